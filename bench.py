@@ -2,9 +2,18 @@
 (BASELINE.json config 2 at N=1; weak-scaled batches per GPU for N>1), plus the
 other BASELINE configs as objects of the same JSON line.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs and no more: it fills the
+batch, runs W warm-up steps, times K steps, writes the last step's reports
+when --dump-outputs is given and prints the line.  --full adds every other
+measurement to the same line: the CPU baseline, the kernel events of the
+warm-up steps (per_kernel, the dominant kernel's roofline), the one-lane
+repeat, the structured images, BASELINE configs 1, 3, 4 and 5, the host-buffer
+and legacy-entry runs (--no-cpu-baseline, --no-one-lane, --no-configs and
+--no-kernel-events take single ones out again).
 
 `--gpus N` without a torchrun environment starts the N ranks itself (a
 torchrun child process, before this process touches the GPU) and exits with
@@ -55,18 +64,24 @@ def parse(argv=None):
                    help="GPU_MAX_HW_QUEUES for this process (set before HIP initialises; 0 keeps the environment's, "
                         "HIP's own default is 4): two lanes drive 4 HIP streams beside HIP's copy traffic (round 5: "
                         "8.60-8.77k images/s with HIP's 4 queues, 8.87-8.97k with 8)")
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline: the CPU baseline, kernel events in the warm-up steps, the one-lane "
+                        "repeat and the other BASELINE configs (default: the headline alone)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the reports of the last timed step (every image of the "
+                        "batch) as DIR/<name>.npy, float64 (dump_reports)")
     p.add_argument("--no-one-lane", action="store_true",
-                   help="skip the one-lane repeat of the headline (one_lane)")
+                   help="--full: skip the one-lane repeat of the headline (one_lane)")
     p.add_argument("--height", type=int, default=3000)
     p.add_argument("--width", type=int, default=4000)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     p.add_argument("--cpu-procs", type=int, default=0,
                    help="CPU baseline processes (0: the affinity set, bounded by the cgroup quota and the box's "
                         "per-GPU CPU share; cpu_topology)")
     p.add_argument("--no-kernel-events", action="store_true",
-                   help="do not bracket kernels with HIP events (roofline then null)")
+                   help="--full: do not bracket kernels with HIP events (roofline then null)")
     p.add_argument("--no-configs", "--no-config3", dest="no_configs", action="store_true",
-                   help="headline only: skip the BASELINE config 3/4/5 objects and the host-buffer runs")
+                   help="--full: skip the BASELINE config 3/4/5 objects and the host-buffer runs")
     p.add_argument("--config4-images", type=int, default=2048, help="config 4 total images (all ranks)")
     p.add_argument("--config5-images", type=int, default=4096, help="config 5 total images (all ranks)")
     p.add_argument("--plan-only", action="store_true",
@@ -427,13 +442,73 @@ def kernel_times(lib, names):
     return out
 
 
-def headline(cx, timed_events=True, kind="uniform", steps=None):
+def dump_reports(outs, n, cfg, path, rank=0):
+    """--dump-outputs: what a caller of phd_report_batch_device receives, the
+    `n` Full_Report_Data of one call, as float64 arrays with the image index
+    first, one .npy file each (rank r > 0 writes <name>.rank<r>.npy):
+    rgb_stats [n, 6] (Br Bg Bb Cr Cg Cb), average_saturation [n], palette_n [n],
+    palette_group_ids / palette_percentages [n, P] and palette_hsv [n, P, 3]
+    (P = the longest palette of the call, at least 100 as to_json pads;
+    entries past an image's palette are -1 / 0), blur_bins [n, angles, radii],
+    blur_vectors_n [n], blur_vectors [n, V, 2] (angle, magnitude; V at least
+    10) and, where the call computed any, sharpness_n [n] and sharpness [n, S].
+    At the default batch that is 14 MB."""
+    import numpy as np
+    from photohive_dsp_amd.structures import Pixel_HSV
+    os.makedirs(path, exist_ok=True)
+    reps = [outs[i].contents for i in range(n)]
+    pal = [r.color_palette.contents for r in reps]
+    vec = [r.blur_vectors.contents for r in reps]
+    shp = [r.sharpness.contents if r.sharpness else None for r in reps]
+    P = max([100] + [c.N for c in pal])
+    V = max([10] + [g.len_vectors for g in vec])
+    S = max([0] + [s.N for s in shp if s is not None])
+    na, nr = cfg.angle_partitions, cfg.radius_partitions
+    a = {"rgb_stats": np.zeros((n, 6)), "average_saturation": np.zeros(n), "palette_n": np.zeros(n),
+         "palette_group_ids": np.full((n, P), -1.0), "palette_percentages": np.zeros((n, P)),
+         "palette_hsv": np.zeros((n, P, 3)), "blur_bins": np.zeros((n, na, nr)), "blur_vectors_n": np.zeros(n),
+         "blur_vectors": np.zeros((n, V, 2))}
+    if S:
+        a["sharpness_n"], a["sharpness"] = np.zeros(n), np.zeros((n, S))
+    hsv_t = np.dtype([("parent_id", np.int32), ("pad", np.int32), ("h", "f8"), ("s", "f8"), ("v", "f8")])
+    assert hsv_t.itemsize == ctypes.sizeof(Pixel_HSV)
+    for i, r in enumerate(reps):
+        st = r.rgb_stats.contents
+        a["rgb_stats"][i] = (st.Br, st.Bg, st.Bb, st.Cr, st.Cg, st.Cb)
+        a["average_saturation"][i] = r.average_saturation
+        c = pal[i]
+        a["palette_n"][i] = c.N
+        if c.N:
+            avg = np.frombuffer(ctypes.string_at(c.averages, c.N * hsv_t.itemsize), dtype=hsv_t)
+            a["palette_group_ids"][i, :c.N] = avg["parent_id"]
+            a["palette_hsv"][i, :c.N] = np.stack([avg["h"], avg["s"], avg["v"]], axis=1)
+            a["palette_percentages"][i, :c.N] = np.ctypeslib.as_array(c.percentages, shape=(c.N,))
+        bp = r.blur_profile.contents
+        assert (bp.num_angle_bins, bp.num_radius_bins) == (na, nr)
+        for k in range(na):
+            a["blur_bins"][i, k] = np.ctypeslib.as_array(bp.bins[k], shape=(nr,))
+        g = vec[i]
+        a["blur_vectors_n"][i] = g.len_vectors
+        for k in range(g.len_vectors):
+            a["blur_vectors"][i, k] = (g.blur_vectors[k].angle, g.blur_vectors[k].magnitude)
+        if shp[i] is not None and shp[i].N:
+            a["sharpness_n"][i] = shp[i].N
+            a["sharpness"][i, :shp[i].N] = np.ctypeslib.as_array(shp[i].sharpness, shape=(shp[i].N,))
+    for name, arr in a.items():
+        np.save(os.path.join(path, name + (f".rank{rank}" if rank else "") + ".npy"), arr)
+    return {name: list(arr.shape) for name, arr in a.items()}
+
+
+def headline(cx, timed_events=True, kind="uniform", steps=None, profile=True, dump=None):
     """Config 2, weak-scaled: B device-resident 4000x3000 images per rank per step.
     timed_events=False: no kernel events in the timed region (the warm-up
     steps still time the candidates).  kind "hblur": SURVEY.md 8(d) row 2(b)'s
     structured images (gradient + disks + 15-px horizontal box blur, synth.py,
     generated on the device; seed 2 + global image index) instead of uniform
-    random bytes."""
+    random bytes.  profile=False (a plain run): plain warm-up steps, no kernel
+    events anywhere, no one-lane steps.  dump: a folder for the reports of the
+    last timed step (dump_reports); that step's reports are freed after the
+    clock has stopped and they are written."""
     args, lib, torch = cx.args, cx.lib, cx.torch
     steps = args.steps if steps is None else steps
     from photohive_dsp_amd.core import make_config
@@ -453,12 +528,13 @@ def headline(cx, timed_events=True, kind="uniform", steps=None):
     outs = (ctypes.POINTER(Full_Report_Data) * B)()
     status = (ctypes.c_int * B)()
 
-    def step():
+    def step(free=True):
         rc = lib.phd_report_batch_device(d_imgs.data_ptr(), B, H, W, img_bytes, ctypes.byref(cfg), outs,
                                          status, None)
         if rc != 0:
             raise RuntimeError(f"report batch failed ({rc}): {cx.last_error()}")
-        lib.phd_free_reports(outs, B)
+        if free:
+            lib.phd_free_reports(outs, B)
 
     # warmup, then one more step per kernel with events around that kernel's
     # launches only (as in the timed region: events around every launch of all
@@ -466,7 +542,7 @@ def headline(cx, timed_events=True, kind="uniform", steps=None):
     # within ~15 %), to find the dominant kernel in steady state
     # The candidates are the three per-image passes (the palette tail runs once
     # per step, ~0.2 ms); the last warmup steps are the profiled ones.
-    cand = [] if args.no_kernel_events else ["fft_cols", "fft_rows", "hsv_stats"][:max(1, args.warmup)]
+    cand = [] if args.no_kernel_events or not profile else ["fft_cols", "fft_rows", "hsv_stats"][:max(1, args.warmup)]
     lanes = lib.phd_set_lanes(0)
     lib.phd_profile_kernels(0)
     for _ in range(max(1, args.warmup) - len(cand)):
@@ -506,8 +582,8 @@ def headline(cx, timed_events=True, kind="uniform", steps=None):
     cx.barrier()
     t0 = time.perf_counter()
     stage = [0.0] * 8
-    for _ in range(steps):
-        step()
+    for k in range(steps):
+        step(free=dump is None or k < steps - 1)
         tm = (ctypes.c_double * 8)()
         lib.phd_last_timings(tm, 8)
         for j in range(8):
@@ -516,6 +592,10 @@ def headline(cx, timed_events=True, kind="uniform", steps=None):
     elapsed = time.perf_counter() - t0
     kern = kernel_times(lib, KERNELS)
     lib.phd_profile_kernels(0)
+    dumped = None
+    if dump is not None and steps > 0:
+        dumped = dump_reports(outs, B, cfg, dump, cx.rank)
+        lib.phd_free_reports(outs, B)
     n_img = B * steps
     km = kern[dom]["total_ms"] if dom in kern else 0.0
     kl = kern[dom]["launches"] if dom in kern else 0
@@ -523,7 +603,7 @@ def headline(cx, timed_events=True, kind="uniform", steps=None):
     del d_imgs
     torch.cuda.empty_cache()
     res = {"merged": m, "dom": dom, "warm": warm, "warm_alone": warm_alone, "warm_steps": nprof, "kern": kern,
-           "steps": steps, "lanes": lanes,
+           "steps": steps, "lanes": lanes, "dumped": dumped,
            "stages": {k: stage[j] / steps for j, k in enumerate(
                ("hsv_stats", "fft_rows_cols", "palette_pass2", "gpu_total", "host_total", "host_enqueue",
                 "host_decisions", "host_assembly"))}}
@@ -889,7 +969,7 @@ def main(argv=None):
         return plan_only(args, world, rank)
     backend = os.environ.get("PHD_BENCH_BACKEND", "nccl")
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # before this process touches the GPU: the baseline's worker processes
         # start from a clean parent
         topo = cpu_topology()
@@ -917,10 +997,10 @@ def main(argv=None):
     dump_maps("ctx")
 
     cx.lib.phd_set_lanes(args.lanes)                  # every config of this run
-    hl = headline(cx)
+    hl = headline(cx, profile=args.full, dump=args.dump_outputs)
     dump_maps("headline")
     extra = {}
-    if hl["lanes"] > 1 and not args.no_one_lane:
+    if args.full and hl["lanes"] > 1 and not args.no_one_lane:
         # the same workload on one lane: each launch alone on the GPU, so the
         # events in its timed region price the dominant kernel (the roofline of
         # the driver's contract); the headline's two lanes share the GPU
@@ -934,7 +1014,7 @@ def main(argv=None):
                 "images_per_s": round(m1["images"] / m1["elapsed"], 1),
                 "ms_per_step": round(1000 * m1["elapsed"] / h1["steps"], 3),
                 "roofline": dominant_roofline(h1, args)}
-    if not args.no_configs:
+    if args.full and not args.no_configs:
         # the same workload on structured images
         hs = headline(cx, timed_events=False, kind="hblur", steps=max(5, args.steps // 5))
         ms = hs["merged"]
@@ -971,6 +1051,7 @@ def main(argv=None):
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(1000 * m["elapsed"] / args.steps, 3),
+            "full": args.full,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -987,9 +1068,13 @@ def main(argv=None):
             line["roofline"] = pipeline_headline_roofline(value, hl, args)
         else:
             line["roofline"] = dominant_roofline(hl, args)
-        line["warmup_kernels_us_per_launch"] = {k: round(v["avg_us"], 2) for k, v in hl["warm"].items()}
-        line["per_kernel"] = per_kernel_roofline(hl["warm_alone"], B, H, W)
+        if args.full:
+            line["warmup_kernels_us_per_launch"] = {k: round(v["avg_us"], 2) for k, v in hl["warm"].items()}
+            line["per_kernel"] = per_kernel_roofline(hl["warm_alone"], B, H, W)
         line["roofline_pipeline"] = pipeline_roofline(value, H, W)
+        if hl["dumped"] is not None:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "step": "last timed step, rank 0's batch",
+                                      "dtype": "float64", "arrays": hl["dumped"]}
         line.update(extra)
         line["vs_baseline_note"] = ("null: BASELINE.md publishes no number for this metric (its only figures are "
                                     "per-stage CPU seconds on an unstated image size, README.md:62-75)")

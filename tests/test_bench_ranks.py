@@ -51,6 +51,41 @@ def test_every_roofline_prices_algorithmic_bytes():
     assert bench.algorithmic_bytes("report", h, w) == 9 * h * w + 32 * h * (w // 2 + 1)
 
 
+def test_plain_run_is_the_default_and_dump_writes_every_report_field(tmp_path):
+    """A plain run (no --full) takes none of the extra legs; dump_reports
+    (--dump-outputs) writes every field of each Full_Report_Data as float64,
+    image index first, padded past an image's own palette."""
+    import ctypes
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from photohive_dsp_amd.core import make_config
+    from photohive_dsp_amd.structures import Full_Report_Data
+    from tests.test_report_host import _report_struct
+    a = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 3
+    assert bench.parse(["--full", "--dump-outputs", "x"]).full is True
+    made = [_report_struct(7, 3), _report_struct(120, 0)]
+    outs = (ctypes.POINTER(Full_Report_Data) * 2)(*[ctypes.pointer(m[0]) for m in made])
+    shapes = bench.dump_reports(outs, 2, make_config(angle_partitions=8, radius_partitions=5), str(tmp_path))
+    got = {p[:-4]: np.load(tmp_path / p) for p in os.listdir(tmp_path)}
+    assert set(got) == set(shapes) and all(v.dtype == np.float64 for v in got.values())
+    assert got["palette_n"].tolist() == [7, 120] and got["palette_hsv"].shape == (2, 120, 3)
+    assert got["palette_group_ids"][0].tolist() == list(range(7)) + [-1] * 113
+    for i, (fr, _, vals) in enumerate(made):
+        np.testing.assert_array_equal(got["blur_bins"][i], np.array(vals))
+        cp, st = fr.color_palette.contents, fr.rgb_stats.contents
+        assert got["rgb_stats"][i].tolist() == [st.Br, st.Bg, st.Bb, st.Cr, st.Cg, st.Cb]
+        assert got["palette_percentages"][i, :cp.N].tolist() == [cp.percentages[k] for k in range(cp.N)]
+        assert got["palette_hsv"][i, cp.N - 1].tolist() == [cp.averages[cp.N - 1].h, cp.averages[cp.N - 1].s,
+                                                            cp.averages[cp.N - 1].v]
+        g = fr.blur_vectors.contents
+        assert got["blur_vectors"][i, 9].tolist() == [g.blur_vectors[9].angle, g.blur_vectors[9].magnitude]
+        assert got["average_saturation"][i] == 0.4321
+    assert got["sharpness_n"].tolist() == [3, 0] and got["sharpness"].shape == (2, 3)
+    assert got["sharpness"][0].tolist() == [made[0][0].sharpness.contents.sharpness[k] for k in range(3)]
+
+
 def test_rehearsal_on_one_card_reports_one_gpu():
     """Two ranks that share one card (a gloo rehearsal on a one-GPU box) are
     2 ranks on 1 GPU in the line, not "2 GPUs" (VERDICT r5 item 7)."""
