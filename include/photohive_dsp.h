@@ -192,6 +192,59 @@ int phd_report_batch_device_mixed(const uint8_t* const* d_images, const int* hei
 int phd_report_batch_u8(const uint8_t* const* images, const int* heights, const int* widths,
                         int n_images, const phd_config* cfg, Full_Report_Data** out, int* status);
 
+/* ---- batch entry points with per-image crop boxes ------------------------
+ * The reference reports the sharpness of caller-given boxes per image:
+ * get_full_report_data takes Crop_Boundaries* salient_characters and returns
+ * Sharpnesses (src/interface.c:73, get_variance_sharpness,
+ * src/filtering.c:151-183).  The three calls below are the batch calls above
+ * plus `crops`, an array of n_images pointers:
+ *  - crops == NULL behaves as the call without boxes;
+ *  - crops[i] == NULL gives a report whose `sharpness` is NULL, as the
+ *    reference does for NULL bounds; N == 0 gives a Sharpnesses with N == 0;
+ *  - an image whose boxes break crop_pgm's bounds (src/image_processing.c:
+ *    215-218; empty or inverted boxes too) fails alone: out[i] = NULL,
+ *    status[i] < 0, phd_last_error names the image and the box; the other
+ *    images are reported.
+ * Every box of every image of a run goes through one kernel launch; a box's
+ * value depends on the image bytes and the box only (not on the batch, the
+ * lanes or the run). */
+
+/* phd_report_batch_device with per-image boxes (src/filtering.c:151-183 as
+ * called from src/interface.c:73). */
+int phd_report_batch_device_crops(const uint8_t* d_rgb, int n_images, int height, int width,
+                                  size_t image_stride, const phd_config* cfg,
+                                  const Crop_Boundaries* const* crops, Full_Report_Data** out, int* status,
+                                  void* stream);
+
+/* phd_report_batch_device_mixed with per-image boxes (src/filtering.c:151-183,
+ * src/interface.c:73). */
+int phd_report_batch_device_mixed_crops(const uint8_t* const* d_images, const int* heights, const int* widths,
+                                        int n_images, const phd_config* cfg,
+                                        const Crop_Boundaries* const* crops, Full_Report_Data** out,
+                                        int* status, void* stream);
+
+/* phd_report_batch_u8 with per-image boxes (src/filtering.c:151-183,
+ * src/interface.c:73). */
+int phd_report_batch_u8_crops(const uint8_t* const* images, const int* heights, const int* widths,
+                              int n_images, const phd_config* cfg, const Crop_Boundaries* const* crops,
+                              Full_Report_Data** out, int* status);
+
+/* The sharpness stage alone (get_variance_sharpness, src/filtering.c:151-183,
+ * as src/interface.c:73 runs it on the full-resolution luma) over n
+ * device-resident RGB8 images of one size.  crops: n_images pointers (NULL =
+ * no boxes for that image).  out is flat, image by image, box by box: the
+ * full report's values.  Any bad box fails the call.  0 or -1. */
+int phd_sharpness_batch_device(const uint8_t* d_rgb, int n_images, int height, int width,
+                               size_t image_stride, const Crop_Boundaries* const* crops, double* out,
+                               void* stream);
+
+/* Validation hook, host only (no GPU): the batched sharpness kernel's tile
+ * plan and merge order (src/filtering.c:151-183 restated per tile, the call
+ * of src/interface.c:73) in plain C++ over one interleaved host RGB8 image;
+ * out[k] per box.  0 or -1. */
+int phd_debug_sharpness_host(const uint8_t* rgb, int height, int width, const Crop_Boundaries* crops,
+                             double* out);
+
 /* Palette intermediates of one device-resident image, for bit-exact checks:
  * hist[TL] (arm_octree quantities), parents[*n_parents] (valid_parents in
  * palette order), kept[*n_parents] (pixels surviving group_irregular_pixels).

@@ -195,55 +195,116 @@ def get_report(pil_image, salient_characters=None, h_partitions=18, s_partitions
     return _finish(ptr, height, width, kw)
 
 
-def get_reports(images, **kw):
-    """Reports for a list of images (any sizes).  Failed images give None."""
+def normalize_salient(salient_characters, n):
+    """The per-image crop boxes of a batch call as the C argument: `None`, or
+    (array of n POINTER(Crop_Boundaries), objects to keep alive for the call).
+    salient_characters: a sequence of length n whose entries are None (no
+    sharpnesses for that image), a Crop_Boundaries, or a list of
+    {"top", "bottom", "left", "right"} dicts (set_bounding_boxes' input; an
+    empty list gives N == 0).  Needs no GPU."""
+    if salient_characters is None:
+        return None
+    entries = list(salient_characters)
+    if len(entries) != n:
+        raise ValueError(f"salient_characters has {len(entries)} entries for {n} images")
+    keep = []
+    arr = (POINTER(Crop_Boundaries) * n)()
+    for i, e in enumerate(entries):
+        if e is None:
+            continue
+        cb = e if isinstance(e, Crop_Boundaries) else set_bounding_boxes(list(e))
+        keep.append(cb)
+        arr[i] = ctypes.pointer(cb)
+    return arr, keep
+
+
+def get_reports(images, salient_characters=None, **kw):
+    """Reports for a list of images (any sizes).  Failed images give None.
+    salient_characters: per-image crop boxes (normalize_salient)."""
     cfg = make_config(**kw)
     arrs = [to_rgb8(im) for im in images]
     n = len(arrs)
+    crops = normalize_salient(salient_characters, n)
     ptrs = (ctypes.c_void_p * n)(*[a.ctypes.data for a in arrs])
     hs = (ctypes.c_int * n)(*[a.shape[0] for a in arrs])
     ws = (ctypes.c_int * n)(*[a.shape[1] for a in arrs])
     outs = (POINTER(Full_Report_Data) * n)()
     st = (ctypes.c_int * n)()
-    lib.phd_report_batch_u8(ptrs, hs, ws, n, ctypes.byref(cfg), outs, st)
+    if crops is None:
+        lib.phd_report_batch_u8(ptrs, hs, ws, n, ctypes.byref(cfg), outs, st)
+    else:
+        lib.phd_report_batch_u8_crops(ptrs, hs, ws, n, ctypes.byref(cfg), crops[0], outs, st)
     return [(_finish(outs[i], hs[i], ws[i], kw) if st[i] == 0 else None) for i in range(n)]
 
 
-def report_device(images, stream=None, **kw):
-    """Reports for a uint8 torch tensor [N, H, W, 3] resident on the current GPU."""
+def report_device(images, stream=None, salient_characters=None, **kw):
+    """Reports for a uint8 torch tensor [N, H, W, 3] resident on the current GPU.
+    salient_characters: per-image crop boxes (normalize_salient)."""
     if images.dtype.itemsize != 1 or images.dim() != 4 or images.shape[3] != 3 or not images.is_contiguous():
         raise ValueError("expected a contiguous uint8 [N, H, W, 3] device tensor")
     n, h, w = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
     cfg = make_config(**kw)
+    crops = normalize_salient(salient_characters, n)
     outs = (POINTER(Full_Report_Data) * n)()
     st = (ctypes.c_int * n)()
     s = _stream_handle(stream)
-    lib.phd_report_batch_device(images.data_ptr(), n, h, w, 0, ctypes.byref(cfg), outs, st, s)
+    if crops is None:
+        lib.phd_report_batch_device(images.data_ptr(), n, h, w, 0, ctypes.byref(cfg), outs, st, s)
+    else:
+        lib.phd_report_batch_device_crops(images.data_ptr(), n, h, w, 0, ctypes.byref(cfg), crops[0], outs, st, s)
     res = [(_finish(outs[i], h, w, kw) if st[i] == 0 else None) for i in range(n)]
     if any(r is None for r in res):
         raise RuntimeError(f"report_device failed: {last_error()}")
     return res
 
 
-def reports_device_mixed(images, stream=None, **kw):
+def reports_device_mixed(images, stream=None, salient_characters=None, **kw):
     """Reports for a list of uint8 torch tensors [H, W, 3] of any sizes resident
     on the current GPU (BASELINE config 5): one batched run per group of
-    same-size images (phd_report_batch_device_mixed)."""
+    same-size images (phd_report_batch_device_mixed).  salient_characters:
+    per-image crop boxes (normalize_salient)."""
     for im in images:
         if im.dtype.itemsize != 1 or im.dim() != 3 or im.shape[2] != 3 or not im.is_contiguous():
             raise ValueError("expected contiguous uint8 [H, W, 3] device tensors")
     n = len(images)
     cfg = make_config(**kw)
+    crops = normalize_salient(salient_characters, n)
     ptrs = (ctypes.c_void_p * n)(*[im.data_ptr() for im in images])
     hs = (ctypes.c_int * n)(*[int(im.shape[0]) for im in images])
     ws = (ctypes.c_int * n)(*[int(im.shape[1]) for im in images])
     outs = (POINTER(Full_Report_Data) * n)()
     st = (ctypes.c_int * n)()
     s = _stream_handle(stream)
-    lib.phd_report_batch_device_mixed(ptrs, hs, ws, n, ctypes.byref(cfg), outs, st, s)
+    if crops is None:
+        lib.phd_report_batch_device_mixed(ptrs, hs, ws, n, ctypes.byref(cfg), outs, st, s)
+    else:
+        lib.phd_report_batch_device_mixed_crops(ptrs, hs, ws, n, ctypes.byref(cfg), crops[0], outs, st, s)
     res = [(_finish(outs[i], hs[i], ws[i], kw) if st[i] == 0 else None) for i in range(n)]
     if any(r is None for r in res):
         raise RuntimeError(f"reports_device_mixed failed: {last_error()}")
+    return res
+
+
+def sharpness_device(images, salient_characters, stream=None):
+    """The sharpness stage alone (get_variance_sharpness, src/filtering.c:151-183)
+    for a uint8 torch tensor [N, H, W, 3] on the current GPU and per-image crop
+    boxes (normalize_salient): a list of N lists, the full report's values
+    ([] for an image without boxes)."""
+    if images.dtype.itemsize != 1 or images.dim() != 4 or images.shape[3] != 3 or not images.is_contiguous():
+        raise ValueError("expected a contiguous uint8 [N, H, W, 3] device tensor")
+    n, h, w = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
+    crops = normalize_salient(salient_characters, n)
+    if crops is None:
+        raise ValueError("sharpness_device needs salient_characters")
+    counts = [crops[0][i].contents.N if crops[0][i] else 0 for i in range(n)]
+    out = (ctypes.c_double * max(1, sum(counts)))()
+    s = _stream_handle(stream)
+    if lib.phd_sharpness_batch_device(images.data_ptr(), n, h, w, 0, crops[0], out, s) != 0:
+        raise RuntimeError(f"sharpness_device failed: {last_error()}")
+    res, k = [], 0
+    for m in counts:
+        res.append([out[k + j] for j in range(m)])
+        k += m
     return res
 
 

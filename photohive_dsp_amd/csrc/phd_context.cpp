@@ -569,6 +569,9 @@ void destroy_context(Context* c) {
     dfree(c->d_inter);
     dfree(c->d_stage);
     dfree(c->d_ptrs);
+    dfree(c->d_sharp);
+    if (c->h_sharp) (void)hipHostFree(c->h_sharp);
+    c->h_sharp = nullptr;
     for (auto& p : c->d_stage2) dfree(p);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     c->h_pin = nullptr;
@@ -639,6 +642,11 @@ void KernelProfiler::end(int slot, hipStream_t st) {
     if (slot < 0) return;
     if (!launch_events().used) pending[slot] = -1;   // no phd_launch took the events
     launch_events() = LaunchEvents{};
+}
+
+int prof_begin_sharp(KernelProfiler* prof, hipStream_t st) { return prof ? prof->begin(kSharp, st) : -1; }
+void prof_end(KernelProfiler* prof, int slot, hipStream_t st) {
+    if (prof) prof->end(slot, st);
 }
 
 LaunchEvents& launch_events() {

@@ -16,6 +16,7 @@
 
 #include "../../include/photohive_dsp.h"
 #include "phd_internal.h"
+#include "sharp_plan.h"
 
 namespace phd {
 
@@ -216,6 +217,12 @@ struct Context {
     void* d_ptrs = nullptr;                        // small device pointer arrays (debug hooks)
     size_t ptrs_bytes = 0;
     size_t stage_bytes = 0;
+    // batched sharpness (sharp_tiles.h): device pointers | box table | prefix |
+    // slice partials (| flat sums), and the pinned copy of the uploaded part
+    void* d_sharp = nullptr;
+    size_t sharp_bytes = 0;
+    void* h_sharp = nullptr;
+    size_t h_sharp_bytes = 0;
     hipEvent_t ev[8] = {};
     // two streams per context: `stream` (K1, then the FFT chain) and `tail`
     // (the A-record download, the palette's second pass -- rules upload, Kcut,
@@ -373,9 +380,19 @@ struct ImageIn {
     const uint8_t* d_img;   // device RGB8, rows of 3*width bytes
 };
 // Run the full report on n same-size device images.  out[i]/status[i] per image.
+// crops: one set of boxes for every image (the single-image entries; two
+// launches per box, sharpness.hip's k_sharp_pass).  img_crops (crops must be
+// NULL): image i's own boxes, NULL entries allowed, already validated
+// (crops_why); every box of the call goes through one batched launch.
 bool run_reports(Context* c, const uint8_t* const* d_imgs, int n, int height, int width,
                  const phd_config& cfg, const Crop_Boundaries* crops, Full_Report_Data** out,
-                 int* status, hipStream_t stream);
+                 int* status, hipStream_t stream, const Crop_Boundaries* const* img_crops = nullptr);
+// The batched sharpness stage of n same-size device images on st: uploads the
+// box table (one copy) and enqueues the two launches.  Box sums go to out0 +
+// img * out_stride + 2 * slot (doubles); out0 == nullptr: to a flat array in
+// the context's own buffer (*flat_dev; plan slots must be flat).
+bool enqueue_sharpness(Context* c, const uint8_t* const* d_imgs, int n, int width, const SharpPlan& plan,
+                       double* out0, long out_stride, hipStream_t st, double** flat_dev = nullptr);
 // Palette intermediates only (for parity tests).
 bool run_palette_trace(Context* c, const uint8_t* d_img, int height, int width, const phd_config& cfg,
                        std::vector<unsigned>* hist, PaletteDecision* dec,

@@ -9,6 +9,8 @@
 
 #include <vector>
 
+#include "sharp_tiles.h"
+
 namespace phd {
 
 // Experiment switches (PHD_* variables of the timing experiments recorded in
@@ -379,10 +381,22 @@ hipError_t launch_fft_cols_ct_batch(const double2* inter, long inter_stride, int
                                     double* fmax_part, long fmax_stride, const double2* tw,
                                     const unsigned long long* sums, long sums_stride, hipStream_t st,
                                     bool pf = true);
+// Per-kernel event timing of the sharpness launches (KernelProfiler, phd_host.h;
+// phd_context.cpp): prof == nullptr or the kernel not in its mask: -1, nothing recorded.
+struct KernelProfiler;
+int prof_begin_sharp(KernelProfiler* prof, hipStream_t st);
+void prof_end(KernelProfiler* prof, int slot, hipStream_t st);
 // Same, the luma from an fp64 plane when pgm != nullptr (planar input).
 hipError_t launch_sharpness_src(const uint8_t* img, const double* pgm, int height, int width, int n, const int* top,
                                 const int* bottom, const int* left, const int* right, const double* k255,
-                                double* sums, hipStream_t st);
+                                double* sums, hipStream_t st, KernelProfiler* prof = nullptr);
+// Every box of every image of a call (sharp_tiles.h): one launch of nslices
+// blocks over the box table (d_boxes[nboxes], d_prefix[nboxes + 1], device
+// copies of a SharpPlan) and one finish launch.  d_parts: nslices partials.
+// Box k's sum f and M2 go to out0 + img * out_stride + 2 * slot (doubles).
+hipError_t launch_sharpness_batch(const uint8_t* const* d_imgs, const SharpBox* d_boxes, const int* d_prefix,
+                                  int nboxes, int nslices, int width, const double* k255, SharpPart* d_parts,
+                                  double* out0, long out_stride, hipStream_t st, KernelProfiler* prof = nullptr);
 
 // ---- fp64 planar input of the legacy entry point (planar.hip) ---------------
 struct PlanarSrc {
@@ -437,6 +451,6 @@ hipError_t launch_fill_structured(uint8_t* dst, int h, int w, uint64_t seed, int
 // sum (f - mean)^2 (sums zeroed by the caller).
 hipError_t launch_sharpness(const uint8_t* img, int height, int width, int n, const int* top,
                             const int* bottom, const int* left, const int* right, const double* k255,
-                            double* sums, hipStream_t st);
+                            double* sums, hipStream_t st, KernelProfiler* prof = nullptr);
 
 }  // namespace phd

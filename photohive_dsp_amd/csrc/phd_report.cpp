@@ -8,6 +8,8 @@
 //   K4  FFT rows, K5 FFT columns      every image        (fft.hip)   || host decides
 //   H2D keep rules;  Kcut; K3 sums    every image        (palette.hip)
 //   sharpness (crops only)                                (sharpness.hip)
+//     shared boxes: two launches per box after each image's column pass;
+//     per-image boxes (batch calls): one batched launch after K1
 //   D2H bins / max / palette sums -> host finalisation (G_s, averages, vectors)
 //
 // The FFT of an image depends only on K1's channel sums (for the DC bias), so
@@ -86,21 +88,49 @@ Layout make_layout(int n, int tl, int nchunks, int nbins, int ncrops, int ncolbl
 
 // shared with the planar path (phd_planar.cpp)
 bool check_crops(const Crop_Boundaries* cb, int height, int width) {
-    if (!cb) return true;
-    if (cb->N < 0 || (cb->N > 0 && (!cb->top || !cb->bottom || !cb->left || !cb->right))) {
-        set_error("Crop_Boundaries has NULL arrays");
-        return false;
-    }
-    for (int k = 0; k < cb->N; k++) {
-        const int t = cb->top[k], b = cb->bottom[k], l = cb->left[k], r = cb->right[k];
-        // crop_pgm's bounds test (src/image_processing.c:215-218); an empty or
-        // inverted box makes the reference divide by zero / misallocate.
-        if (r > width || l > width || b > height || t > height || l < 0 || r < 0 || t < 0 || b < 0 ||
-            r <= l || b <= t) {
-            set_error("crop boundaries outside of image boundaries (crop " + std::to_string(k) + ")");
+    // the rules: crops_why (phd_sharp_host.cpp)
+    std::string why;
+    if (crops_why(cb, height, width, &why)) return true;
+    set_error(why);
+    return false;
+}
+
+bool enqueue_sharpness(Context* c, const uint8_t* const* d_imgs, int n, int width, const SharpPlan& plan,
+                       double* out0, long out_stride, hipStream_t st, double** flat_dev) {
+    const int nb = (int)plan.boxes.size();
+    if (flat_dev) *flat_dev = nullptr;
+    if (nb == 0) return true;
+    const int nslices = plan.prefix[nb];
+    // uploaded: image pointers | boxes | prefix; device only: partials | flat sums
+    const size_t o_box = al(sizeof(void*) * (size_t)n);
+    const size_t o_pre = o_box + al(sizeof(SharpBox) * (size_t)nb);
+    const size_t up = o_pre + al(sizeof(int) * ((size_t)nb + 1));
+    const size_t o_flat = up + al(sizeof(SharpPart) * (size_t)nslices);
+    const size_t total = o_flat + (out0 ? 0 : al(2 * sizeof(double) * (size_t)nb));
+    if (!ensure_device(&c->d_sharp, &c->sharp_bytes, total)) return false;
+    if (c->h_sharp_bytes < up) {
+        // (every call drains its streams before it returns: no copy reads the old block)
+        if (c->h_sharp) (void)hipHostFree(c->h_sharp);
+        c->h_sharp = nullptr;
+        c->h_sharp_bytes = 0;
+        const size_t sz = up + up / 4 + 4096;
+        if (hipHostMalloc(&c->h_sharp, sz, hipHostMallocDefault) != hipSuccess) {
+            set_error("hipHostMalloc failed");
             return false;
         }
+        c->h_sharp_bytes = sz;
     }
+    uint8_t* hs = (uint8_t*)c->h_sharp;
+    uint8_t* ds = (uint8_t*)c->d_sharp;
+    memcpy(hs, d_imgs, sizeof(void*) * (size_t)n);
+    memcpy(hs + o_box, plan.boxes.data(), sizeof(SharpBox) * (size_t)nb);
+    memcpy(hs + o_pre, plan.prefix.data(), sizeof(int) * ((size_t)nb + 1));
+    PHD_HIP(hipMemcpyAsync(ds, hs, up, hipMemcpyHostToDevice, st));
+    double* dst = out0 ? out0 : (double*)(ds + o_flat);
+    if (flat_dev) *flat_dev = dst;
+    PHD_HIP(launch_sharpness_batch((const uint8_t* const*)ds, (const SharpBox*)(ds + o_box), (const int*)(ds + o_pre),
+                                   nb, nslices, width, c->d_k255, (SharpPart*)(ds + up), dst, out0 ? out_stride : 0,
+                                   st, &c->prof));
     return true;
 }
 
@@ -444,7 +474,7 @@ bool fused_slot_sums(const GridParams& gp, const PaletteDecision& dec, const uns
 
 bool run_reports(Context* c, const uint8_t* const* d_imgs, int n, int height, int width,
                  const phd_config& cfg, const Crop_Boundaries* crops, Full_Report_Data** out, int* status,
-                 hipStream_t stream) {
+                 hipStream_t stream, const Crop_Boundaries* const* img_crops) {
     const auto t_host0 = std::chrono::steady_clock::now();
     for (int i = 0; i < n; i++) {
         out[i] = nullptr;
@@ -456,6 +486,20 @@ bool run_reports(Context* c, const uint8_t* const* d_imgs, int n, int height, in
         return false;
     }
     if (!precheck(height, width) || !check_crops(crops, height, width)) return false;
+    // per-image boxes: the whole call's box table (one batched launch)
+    SharpPlan splan;
+    if (img_crops) {
+        if (crops) {
+            set_error("run_reports: shared and per-image crop boxes together");
+            return false;
+        }
+        for (int i = 0; i < n; i++)
+            if (!check_crops(img_crops[i], height, width)) return false;
+        if (!sharp_plan(img_crops, n, false, &splan)) {
+            set_error("too many crop boxes in one call");
+            return false;
+        }
+    }
     const hipStream_t st = work_stream(c, stream);
     // ev_img_fft only orders the download stream after a column pass on this
     // device (device_event_flags: no system-scope fence)
@@ -508,7 +552,8 @@ bool run_reports(Context* c, const uint8_t* const* d_imgs, int n, int height, in
     static const int dl_group = phd_knob("PHD_DL_GROUP") ? std::max(1, atoi(phd_knob("PHD_DL_GROUP"))) : 2;
     // fused palette (one pixel pass): ds == 1 and the fused K1's LDS fits; else K1 + K3
     const bool fused = ds <= 1 && fused_palette_ok(gp);
-    const Layout L = make_layout(n, gp.tl, nchunks, nbins, ncrops, ncolblocks, fused ? HueCells::count(gp) : 0);
+    const Layout L = make_layout(n, gp.tl, nchunks, nbins, img_crops ? splan.max_boxes : ncrops, ncolblocks,
+                                 fused ? HueCells::count(gp) : 0);
     // half-spectrum intermediates: one per image of a group of Q (the group's row
     // passes run before its column passes); large images one at a time, so the
     // intermediate stays in the 256 MB MALL between its two passes (round 2:
@@ -573,6 +618,11 @@ bool run_reports(Context* c, const uint8_t* const* d_imgs, int n, int height, in
     // ~20 us between K1 and the first row pass.
     const hipStream_t sf = st;
     const size_t inter_elems = inter_one / sizeof(double2);
+    // per-image boxes: every box of the call once, ahead of the FFTs (and so of
+    // every download group's event); the sums land in the images' C records
+    if (img_crops && !enqueue_sharpness(c, d_imgs, n, width, splan, (double*)(dw + L.C(n, 0) + L.c_sharp),
+                                        (long)(L.c_bytes / 8), sf))
+        return false;
     for (int g0 = 0; gbatch && g0 < n; g0 += Q) {
         const int g1 = std::min(n, g0 + Q);
         const uint8_t* const* d_ptrs = (const uint8_t* const*)(dw + L.P_dev(n));
@@ -592,7 +642,7 @@ bool run_reports(Context* c, const uint8_t* const* d_imgs, int n, int height, in
                 PHD_HIP(launch_sharpness(d_imgs[i], height, width, ncrops, crop_arr.data(),
                                          crop_arr.data() + ncrops, crop_arr.data() + 2 * ncrops,
                                          crop_arr.data() + 3 * ncrops, c->d_k255,
-                                         (double*)(dw + L.C(n, i) + L.c_sharp), sf));
+                                         (double*)(dw + L.C(n, i) + L.c_sharp), sf, &c->prof));
             if (dl_end(i)) PHD_HIP(hipEventRecord(c->ev_img_fft[i], sf));
         }
     }
@@ -615,7 +665,7 @@ bool run_reports(Context* c, const uint8_t* const* d_imgs, int n, int height, in
                 PHD_HIP(launch_sharpness(d_imgs[i], height, width, ncrops, crop_arr.data(),
                                          crop_arr.data() + ncrops, crop_arr.data() + 2 * ncrops,
                                          crop_arr.data() + 3 * ncrops, c->d_k255,
-                                         (double*)(dw + L.C(n, i) + L.c_sharp), sf));
+                                         (double*)(dw + L.C(n, i) + L.c_sharp), sf, &c->prof));
             if (dl_end(i)) PHD_HIP(hipEventRecord(c->ev_img_fft[i], sf));
         }
     }
@@ -650,7 +700,7 @@ bool run_reports(Context* c, const uint8_t* const* d_imgs, int n, int height, in
                 PHD_HIP(launch_sharpness(d_imgs[i], height, width, ncrops, crop_arr.data(),
                                          crop_arr.data() + ncrops, crop_arr.data() + 2 * ncrops,
                                          crop_arr.data() + 3 * ncrops, c->d_k255,
-                                         (double*)(dw + L.C(n, i) + L.c_sharp), sf));
+                                         (double*)(dw + L.C(n, i) + L.c_sharp), sf, &c->prof));
             }
             if (dl_end(i) && !recorded) PHD_HIP(hipEventRecord(c->ev_img_fft[i], sf));
         }
@@ -852,8 +902,8 @@ bool run_reports(Context* c, const uint8_t* const* d_imgs, int n, int height, in
             pal = hsum[i].data();
         }
         out[i] = assemble(st_i, s_acc / (double)n_hsv, dec[i], pal, n_hsv, *tbl,
-                          (const unsigned long long*)(cc + L.c_bins), fmax, cfg, crops,
-                          (const double*)(cc + L.c_sharp), &asm_why[i]);
+                          (const unsigned long long*)(cc + L.c_bins), fmax, cfg,
+                          img_crops ? img_crops[i] : crops, (const double*)(cc + L.c_sharp), &asm_why[i]);
         if (out[i]) status[i] = 0;
     };
     for (int i0 = 0; i0 < n; i0 = dl_last(i0) + 1) {
@@ -1444,9 +1494,9 @@ extern "C" int phd_report_batch_device_mixed(const uint8_t* const* d_images, con
 // of two device staging buffers and reported as one batch; the next group's
 // upload (pinned slot ring, copy threads + DMA) runs on an uploader thread
 // while the current group computes.
-extern "C" int phd_report_batch_u8(const uint8_t* const* images, const int* heights, const int* widths,
-                                   int n_images, const phd_config* cfg, Full_Report_Data** out, int* status) {
-    clear_error();
+static int report_batch_u8(const uint8_t* const* images, const int* heights, const int* widths, int n_images,
+                           const phd_config* cfg, const Crop_Boundaries* const* crops, Full_Report_Data** out,
+                           int* status) {
     if (!images || !heights || !widths || !cfg || !out || !status || n_images <= 0) {
         set_error("phd_report_batch_u8: bad arguments");
         return -1;
@@ -1523,7 +1573,12 @@ extern "C" int phd_report_batch_u8(const uint8_t* const* images, const int* heig
         std::vector<int> st(m, -1);
         if (!ups[gi].ok) set_error(ups[gi].why);
         else if (hipStreamWaitEvent(c->stream, c->ev_up[b], 0) != hipSuccess) set_error("upload ordering failed");
-        else run_reports(c, ptrs.data(), m, h, w, *cfg, nullptr, o.data(), st.data(), nullptr);
+        else if (!crops) run_reports(c, ptrs.data(), m, h, w, *cfg, nullptr, o.data(), st.data(), nullptr);
+        else {
+            std::vector<const Crop_Boundaries*> cr(m);
+            for (int k = 0; k < m; k++) cr[k] = crops[g[k]];
+            run_reports(c, ptrs.data(), m, h, w, *cfg, nullptr, o.data(), st.data(), nullptr, cr.data());
+        }
         for (int k = 0; k < m; k++) {
             out[g[k]] = o[k];
             status[g[k]] = st[k];
@@ -1536,6 +1591,208 @@ extern "C" int phd_report_batch_u8(const uint8_t* const* images, const int* heig
     (void)hipStreamSynchronize(c->stream);
     for (int i = 0; i < n_images; i++) fails += status[i] != 0;
     return fails;
+}
+
+extern "C" int phd_report_batch_u8(const uint8_t* const* images, const int* heights, const int* widths,
+                                   int n_images, const phd_config* cfg, Full_Report_Data** out, int* status) {
+    clear_error();
+    return report_batch_u8(images, heights, widths, n_images, cfg, nullptr, out, status);
+}
+
+// ---- batch entry points with per-image crop boxes ---------------------------
+// (get_variance_sharpness, src/filtering.c:151-183, as get_full_report_data
+// calls it, src/interface.c:73)
+
+// The images of a call whose boxes pass check_crops' rules (`keep`, in order).
+// An image with a bad box fails alone: out NULL, status -1, and the message
+// (the last one stays in phd_last_error) names the image and the box.
+static std::vector<int> valid_box_images(const Crop_Boundaries* const* crops, const int* heights, const int* widths,
+                                         int height, int width, int n, Full_Report_Data** out, int* status) {
+    std::vector<int> keep;
+    std::string bad;
+    for (int i = 0; i < n; i++) {
+        out[i] = nullptr;
+        status[i] = -1;
+        std::string why;
+        if (crops_why(crops[i], heights ? heights[i] : height, widths ? widths[i] : width, &why)) keep.push_back(i);
+        else bad = "image " + std::to_string(i) + ": " + why;
+    }
+    if (!bad.empty()) set_error(bad);
+    return keep;
+}
+
+extern "C" int phd_report_batch_device_crops(const uint8_t* d_rgb, int n_images, int height, int width,
+                                             size_t image_stride, const phd_config* cfg,
+                                             const Crop_Boundaries* const* crops, Full_Report_Data** out,
+                                             int* status, void* stream) {
+    if (!crops) return phd_report_batch_device(d_rgb, n_images, height, width, image_stride, cfg, out, status, stream);
+    clear_error();
+    if (!d_rgb || !cfg || !out || !status || n_images <= 0) {
+        set_error("phd_report_batch_device_crops: bad arguments");
+        return -1;
+    }
+    Context* c = get_context();
+    if (!c) return -1;
+    const std::vector<int> keep = valid_box_images(crops, nullptr, nullptr, height, width, n_images, out, status);
+    const size_t stride = image_stride ? image_stride : 3 * (size_t)width * height;
+    const int m = (int)keep.size();
+    std::vector<const uint8_t*> imgs(m);
+    std::vector<const Crop_Boundaries*> cr(m);
+    std::vector<Full_Report_Data*> o(m, nullptr);
+    std::vector<int> stt(m, -1);
+    for (int k = 0; k < m; k++) {
+        imgs[k] = d_rgb + (size_t)keep[k] * stride;
+        cr[k] = crops[keep[k]];
+    }
+    // the lanes as in phd_report_batch_device, each with its images' part of the table
+    if (m > 0)
+        on_lanes(c, m >= 16 && !stream, [&](Context* cl, int lane, int nl) {
+            const int h = nl == 2 ? (int)(((long)m * 131 + 128) / 256) : m;
+            const int i0 = lane ? h : 0, mm = lane ? m - h : h;
+            run_reports(cl, imgs.data() + i0, mm, height, width, *cfg, nullptr, o.data() + i0, stt.data() + i0,
+                        (hipStream_t)stream, cr.data() + i0);
+        });
+    for (int k = 0; k < m; k++) {
+        out[keep[k]] = o[k];
+        status[keep[k]] = stt[k];
+    }
+    int fails = 0;
+    for (int i = 0; i < n_images; i++) fails += status[i] != 0;
+    return fails;
+}
+
+extern "C" int phd_report_batch_device_mixed_crops(const uint8_t* const* d_images, const int* heights,
+                                                   const int* widths, int n_images, const phd_config* cfg,
+                                                   const Crop_Boundaries* const* crops, Full_Report_Data** out,
+                                                   int* status, void* stream) {
+    if (!crops) return phd_report_batch_device_mixed(d_images, heights, widths, n_images, cfg, out, status, stream);
+    clear_error();
+    if (!d_images || !heights || !widths || !cfg || !out || !status || n_images <= 0) {
+        set_error("phd_report_batch_device_mixed_crops: bad arguments");
+        return -1;
+    }
+    Context* c = get_context();
+    if (!c) return -1;
+    const std::vector<int> keep = valid_box_images(crops, heights, widths, 0, 0, n_images, out, status);
+    const int m = (int)keep.size();
+    std::vector<int> hs(m), ws(m);
+    for (int k = 0; k < m; k++) {
+        hs[k] = heights[keep[k]];
+        ws[k] = widths[keep[k]];
+    }
+    const auto groups = size_groups(hs.data(), ws.data(), m, 64, 64L * 12000000L);
+    std::atomic<size_t> next{0};
+    if (m > 0)
+        on_lanes(c, groups.size() >= 2 && !stream, [&](Context* cl, int, int) {
+            for (size_t gi; (gi = next.fetch_add(1)) < groups.size();) {
+                const auto& grp = groups[gi];
+                const int gm = (int)grp.size();
+                std::vector<const uint8_t*> ptrs(gm);
+                std::vector<const Crop_Boundaries*> cr(gm);
+                std::vector<Full_Report_Data*> o(gm, nullptr);
+                std::vector<int> st(gm, -1);
+                for (int k = 0; k < gm; k++) {
+                    ptrs[k] = d_images[keep[grp[k]]];
+                    cr[k] = crops[keep[grp[k]]];
+                }
+                run_reports(cl, ptrs.data(), gm, hs[grp[0]], ws[grp[0]], *cfg, nullptr, o.data(), st.data(),
+                            (hipStream_t)stream, cr.data());
+                for (int k = 0; k < gm; k++) {
+                    out[keep[grp[k]]] = o[k];
+                    status[keep[grp[k]]] = st[k];
+                }
+            }
+        });
+    int fails = 0;
+    for (int i = 0; i < n_images; i++) fails += status[i] != 0;
+    return fails;
+}
+
+extern "C" int phd_report_batch_u8_crops(const uint8_t* const* images, const int* heights, const int* widths,
+                                         int n_images, const phd_config* cfg, const Crop_Boundaries* const* crops,
+                                         Full_Report_Data** out, int* status) {
+    clear_error();
+    if (!crops) return report_batch_u8(images, heights, widths, n_images, cfg, nullptr, out, status);
+    if (!images || !heights || !widths || !cfg || !out || !status || n_images <= 0) {
+        set_error("phd_report_batch_u8_crops: bad arguments");
+        return -1;
+    }
+    const std::vector<int> keep = valid_box_images(crops, heights, widths, 0, 0, n_images, out, status);
+    const int m = (int)keep.size();
+    std::vector<const uint8_t*> im(m);
+    std::vector<int> hs(m), ws(m), stt(m, -1);
+    std::vector<const Crop_Boundaries*> cr(m);
+    std::vector<Full_Report_Data*> o(m, nullptr);
+    for (int k = 0; k < m; k++) {
+        im[k] = images[keep[k]];
+        hs[k] = heights[keep[k]];
+        ws[k] = widths[keep[k]];
+        cr[k] = crops[keep[k]];
+    }
+    const int rc = m > 0 ? report_batch_u8(im.data(), hs.data(), ws.data(), m, cfg, cr.data(), o.data(), stt.data())
+                         : 0;
+    for (int k = 0; k < m; k++) {
+        out[keep[k]] = o[k];
+        status[keep[k]] = stt[k];
+    }
+    if (rc < 0) return -1;
+    int fails = 0;
+    for (int i = 0; i < n_images; i++) fails += status[i] != 0;
+    return fails;
+}
+
+// The sharpness stage alone over n same-size device images, as
+// phd_blur_batch_device runs its stage: one batched launch for every box of
+// the call, then var / mean per box on the host (the full report's values).
+extern "C" int phd_sharpness_batch_device(const uint8_t* d_rgb, int n_images, int height, int width,
+                                          size_t image_stride, const Crop_Boundaries* const* crops, double* out,
+                                          void* stream) {
+    clear_error();
+    if (!d_rgb || !crops || n_images <= 0 || height <= 0 || width <= 0) {
+        set_error("phd_sharpness_batch_device: bad arguments");
+        return -1;
+    }
+    for (int i = 0; i < n_images; i++) {
+        std::string why;
+        if (!crops_why(crops[i], height, width, &why)) {
+            set_error("image " + std::to_string(i) + ": " + why);
+            return -1;
+        }
+    }
+    SharpPlan plan;
+    if (!sharp_plan(crops, n_images, true, &plan)) {
+        set_error("too many crop boxes in one call");
+        return -1;
+    }
+    const size_t nb = plan.boxes.size();
+    if (nb == 0) return 0;
+    if (!out) {
+        set_error("phd_sharpness_batch_device: bad arguments");
+        return -1;
+    }
+    Context* c = get_context();
+    if (!c) return -1;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const hipStream_t st = work_stream(c, stream);
+    const size_t stride = image_stride ? image_stride : 3 * (size_t)width * height;
+    std::vector<const uint8_t*> imgs(n_images);
+    for (int i = 0; i < n_images; i++) imgs[i] = d_rgb + (size_t)i * stride;
+    if (!ensure_pinned(c, 2 * sizeof(double) * nb)) return -1;
+    double* d_flat = nullptr;
+    if (!enqueue_sharpness(c, imgs.data(), n_images, width, plan, nullptr, 0, st, &d_flat)) return -1;
+    hipError_t e;
+    if ((e = hipMemcpyAsync(c->h_pin, d_flat, 2 * sizeof(double) * nb, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+        (e = hipStreamSynchronize(st)) != hipSuccess) {
+        set_error(std::string("phd_sharpness_batch_device: ") + hipGetErrorString(e));
+        return -1;
+    }
+    c->prof.collect();
+    const double* sums = (const double*)c->h_pin;
+    for (size_t k = 0; k < nb; k++) {
+        const SharpBox& b = plan.boxes[k];
+        out[k] = sharp_value(sums[2 * k], sums[2 * k + 1], b.right - b.left, b.bottom - b.top);
+    }
+    return 0;
 }
 
 extern "C" int phd_palette_trace_device(const uint8_t* d_rgb, int height, int width, const phd_config* cfg,

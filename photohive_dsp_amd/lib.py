@@ -128,14 +128,31 @@ lib.free_full_report.argtypes = [P(P(Full_Report_Data))]
 lib.phd_free_reports.restype = None
 lib.phd_free_reports.argtypes = [P(P(Full_Report_Data)), ctypes.c_int]
 lib.phd_free_pgm.argtypes = [P(Image_PGM)]
-# round-6 entry points, bound only when present: an A/B timing run may load an
+# round-6 and later entry points, bound only when present: an A/B timing run may load an
 # older build through PHD_LIB (tools/); the shipped library exports all of them
 # (tests/test_abi.py checks every symbol of include/photohive_dsp.h)
 for _name, _res, _args in (("phd_shutdown", None, []),
                            ("phd_install_crash_maps", ctypes.c_int, [ctypes.c_char_p]),
                            ("phd_debug_library_threads", ctypes.c_int, [ctypes.c_int]),
                            ("phd_debug_legacy_report", P(Full_Report_Data),
-                            [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int])):
+                            [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+                           # batch calls with per-image crop boxes (crops: n pointers to Crop_Boundaries)
+                           ("phd_report_batch_device_crops", ctypes.c_int,
+                            [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_size_t,
+                             P(PhdConfig), P(P(Crop_Boundaries)), P(P(Full_Report_Data)), P(ctypes.c_int),
+                             ctypes.c_void_p]),
+                           ("phd_report_batch_device_mixed_crops", ctypes.c_int,
+                            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, P(PhdConfig),
+                             P(P(Crop_Boundaries)), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+                           ("phd_report_batch_u8_crops", ctypes.c_int,
+                            [P(ctypes.c_void_p), P(ctypes.c_int), P(ctypes.c_int), ctypes.c_int, P(PhdConfig),
+                             P(P(Crop_Boundaries)), P(P(Full_Report_Data)), P(ctypes.c_int)]),
+                           ("phd_sharpness_batch_device", ctypes.c_int,
+                            [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_size_t,
+                             P(P(Crop_Boundaries)), P(ctypes.c_double), ctypes.c_void_p]),
+                           ("phd_debug_sharpness_host", ctypes.c_int,
+                            [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, P(Crop_Boundaries),
+                             P(ctypes.c_double)])):
     try:
         _f = getattr(lib, _name)
     except AttributeError:
