@@ -245,6 +245,56 @@ int phd_sharpness_batch_device(const uint8_t* d_rgb, int n_images, int height, i
 int phd_debug_sharpness_host(const uint8_t* rgb, int height, int width, const Crop_Boundaries* crops,
                              double* out);
 
+/* ---- device images in any byte-strided layout ------------------------------
+ * The reference takes three independent plane pointers (Image_RGB,
+ * src/image_processing.h:31-36); the device calls above take interleaved RGB8
+ * with rows of 3*width bytes only.  A view describes what GPU producers emit
+ * -- planar, pitched rows, RGBA / BGRA, BGR, a region of a larger frame, an
+ * expanded grey plane -- and the library gathers it once into a packed image
+ * of its own (one launch per run for all its views); a view that is already
+ * packed is read in place. */
+
+/* One device-resident 8-bit image as a byte-strided view: channel c (0 = R,
+ * 1 = G, 2 = B) of pixel (y, x) is the byte at
+ *   data + y*row_stride + x*pixel_stride + c*channel_stride.
+ * Strides are in bytes and may be negative or 0.  (row, pixel, channel):
+ * packed HWC (3W, 3, 1); pitched HWC (pitch, 3, 1); RGBA / RGBX (pitch, 4, 1);
+ * BGR (pitch, 3, -1) with data at the R byte; BGRA (pitch, 4, -1), data at +2;
+ * ARGB data at +1; planar CHW (W or pitch, 1, plane stride); an expanded grey
+ * plane (W, 1, 0); any region of interest of these.
+ * Valid: data non-NULL, height and width > 0, pixel_stride != 0 when width > 1,
+ * row_stride != 0 when height > 1. */
+typedef struct phd_image_view {
+    const uint8_t* data;
+    int height, width;
+    int64_t row_stride, pixel_stride, channel_stride;
+} phd_image_view;
+
+/* phd_report_batch_device_mixed_crops over views (get_full_report_data,
+ * src/interface.c:20-94, per image): any sizes, crops may be NULL, boxes in the
+ * view's own coordinates, the reference's size checks (src/utilities.c:64-87)
+ * on the view's height and width.  A bad view fails alone like bad boxes:
+ * out[i] = NULL, status[i] < 0, phd_last_error names the image and the field.
+ * No byte outside a view's span (lowest to highest addressed byte) is read.
+ * Returns as that call. */
+int phd_report_batch_device_views(const phd_image_view* views, int n_images, const phd_config* cfg,
+                                  const Crop_Boundaries* const* crops, Full_Report_Data** out, int* status,
+                                  void* stream);
+
+/* The gather alone: d_dst[i] (device) receives the 3*height*width packed RGB8
+ * bytes of view i; any size from 1x1.  For the stage-only calls
+ * (phd_blur_batch_device, phd_hsv_stats_batch_device,
+ * phd_sharpness_batch_device), which take packed input.  Enqueued on `stream`,
+ * or (NULL) on the library's stream and waited for.  A bad view fails the
+ * call.  0 or -1. */
+int phd_pack_views_device(const phd_image_view* views, int n_images, uint8_t* const* d_dst, void* stream);
+
+/* Validation hook, host only (no GPU): the pack kernel's gather (the reference
+ * reads its planes per pixel, src/image_processing.c:387; here the row
+ * split and addresses of pack_view.h) over one view of host memory into
+ * dst[3*height*width].  0 or -1. */
+int phd_debug_pack_view_host(const phd_image_view* view, uint8_t* dst);
+
 /* Palette intermediates of one device-resident image, for bit-exact checks:
  * hist[TL] (arm_octree quantities), parents[*n_parents] (valid_parents in
  * palette order), kept[*n_parents] (pixels surviving group_irregular_pixels).
@@ -337,7 +387,8 @@ int phd_last_timings(double* ms, int n);
 
 /* Per-kernel GPU time from HIP events recorded on the launch stream around
  * every launch of the kernels in `mask` (bit k = kernel k: 0 hsv_stats,
- * 1 fft_rows, 2 fft_cols, 3 palette_cutoffs, 4 palette_sums, 5 sharpness).
+ * 1 fft_rows, 2 fft_cols, 3 palette_cutoffs, 4 palette_sums, 5 sharpness,
+ * 6 pack_views).
  * phd_profile_kernels resets the counters; phd_profile_read returns the
  * accumulated milliseconds and launch count of one kernel. */
 int phd_profile_kernels(unsigned mask);

@@ -18,7 +18,7 @@ from types import SimpleNamespace
 import numpy as np
 
 from .lib import last_error, lib
-from .structures import Crop_Boundaries, Full_Report_Data, PhdConfig, Pixel_HSV, RGB_Statistics
+from .structures import Crop_Boundaries, Full_Report_Data, PhdConfig, PhdImageView, Pixel_HSV, RGB_Statistics
 from .utils import hsv_to_rgb, image_pgm_to_pillow, to_rgb8
 
 DEFAULTS = dict(h_partitions=18, s_partitions=2, v_partitions=3, black_thresh=0.1, gray_thresh=0.1,
@@ -283,6 +283,85 @@ def reports_device_mixed(images, stream=None, salient_characters=None, **kw):
     if any(r is None for r in res):
         raise RuntimeError(f"reports_device_mixed failed: {last_error()}")
     return res
+
+
+def make_views(tensors, layout="HWC", bgr=False):
+    """The PhdImageView descriptors of uint8 torch tensors, with no copy: a
+    sequence of [H, W, C] (C = 3 or 4; layout "HWC") or [C, H, W] ("CHW")
+    tensors of any strides, or one 4-D tensor taken as its images.  Channels
+    0..2 are R, G, B; bgr=True reverses them (data at channel 2, the channel
+    stride negated).  An entry that is a PhdImageView already is taken as it
+    is (a call that mixes layouts, or memory that is no tensor).  Pure stride
+    arithmetic on data_ptr() and stride(): needs no GPU (CPU tensors work).
+    Returns (array of PhdImageView, objects to keep alive while the views are
+    in use)."""
+    import torch
+    if layout not in ("HWC", "CHW"):
+        raise ValueError(f"layout must be 'HWC' or 'CHW', not {layout!r}")
+    if isinstance(tensors, torch.Tensor):
+        if tensors.dim() != 4:
+            raise ValueError("a single tensor must be 4-D (a batch of images)")
+        tensors = list(tensors.unbind(0))
+    tensors = list(tensors)
+    views = (PhdImageView * max(1, len(tensors)))()
+    for i, t in enumerate(tensors):
+        if isinstance(t, PhdImageView):
+            views[i] = t
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+            raise ValueError(f"image {i}: expected a uint8 torch tensor")
+        if t.dim() != 3:
+            raise ValueError(f"image {i}: expected 3 dimensions ({layout}), got {t.dim()}")
+        if layout == "HWC":
+            (h, w, ch), (rs, ps, cs) = t.shape, t.stride()
+        else:
+            (ch, h, w), (cs, rs, ps) = t.shape, t.stride()
+        if ch not in (3, 4):
+            raise ValueError(f"image {i}: expected 3 or 4 channels, got {ch}")
+        data = t.data_ptr()                      # uint8: element strides are byte strides
+        if bgr:
+            data, cs = data + 2 * cs, -cs
+        views[i] = PhdImageView(data, int(h), int(w), int(rs), int(ps), int(cs))
+    return views, tensors
+
+
+def reports_device_views(images, layout="HWC", bgr=False, stream=None, salient_characters=None, **kw):
+    """Reports for uint8 device tensors in any byte-strided layout (make_views:
+    planar CHW, pitched rows, RGBA / BGRA, BGR, regions of interest, expanded
+    grey planes; any sizes), without a repacked copy on the caller's side:
+    views that are not packed RGB8 already are gathered into a library-owned
+    staging image by one launch per run (phd_report_batch_device_views).
+    salient_characters: per-image crop boxes in each view's own coordinates
+    (normalize_salient)."""
+    views, keep = make_views(images, layout, bgr)
+    n = len(keep)
+    cfg = make_config(**kw)
+    crops = normalize_salient(salient_characters, n)
+    outs = (POINTER(Full_Report_Data) * n)()
+    st = (ctypes.c_int * n)()
+    s = _stream_handle(stream)
+    lib.phd_report_batch_device_views(views, n, ctypes.byref(cfg), crops[0] if crops else None, outs, st, s)
+    res = [(_finish(outs[i], views[i].height, views[i].width, kw) if st[i] == 0 else None) for i in range(n)]
+    if any(r is None for r in res):
+        raise RuntimeError(f"reports_device_views failed: {last_error()}")
+    return res
+
+
+def pack_views_device(images, layout="HWC", bgr=False, stream=None):
+    """The gather alone (phd_pack_views_device): packed [H, W, 3] uint8 device
+    tensors of the given views (make_views), for the stage-only calls
+    (sharpness_device, hsv_stats_device, blur_profiles_device)."""
+    import torch
+    views, keep = make_views(images, layout, bgr)
+    n = len(keep)
+    if n == 0:
+        return []
+    out = [torch.empty((views[i].height, views[i].width, 3), dtype=torch.uint8,
+                       device=keep[i].device if isinstance(keep[i], torch.Tensor) else "cuda") for i in range(n)]
+    dst = (ctypes.c_void_p * n)(*[o.data_ptr() for o in out])
+    if lib.phd_pack_views_device(views, n, dst, _stream_handle(stream)) != 0:
+        raise RuntimeError(f"pack_views_device failed: {last_error()}")
+    return out
 
 
 def sharpness_device(images, salient_characters, stream=None):

@@ -572,6 +572,11 @@ void destroy_context(Context* c) {
     dfree(c->d_sharp);
     if (c->h_sharp) (void)hipHostFree(c->h_sharp);
     c->h_sharp = nullptr;
+    dfree(c->d_vstage);
+    dfree(c->d_views);
+    if (c->h_views) (void)hipHostFree(c->h_views);
+    c->h_views = nullptr;
+    ev_destroy(c->ev_views);
     for (auto& p : c->d_stage2) dfree(p);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     c->h_pin = nullptr;
@@ -645,6 +650,7 @@ void KernelProfiler::end(int slot, hipStream_t st) {
 }
 
 int prof_begin_sharp(KernelProfiler* prof, hipStream_t st) { return prof ? prof->begin(kSharp, st) : -1; }
+int prof_begin_pack(KernelProfiler* prof, hipStream_t st) { return prof ? prof->begin(kPack, st) : -1; }
 void prof_end(KernelProfiler* prof, int slot, hipStream_t st) {
     if (prof) prof->end(slot, st);
 }

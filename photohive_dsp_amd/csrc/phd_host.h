@@ -17,6 +17,7 @@
 #include "../../include/photohive_dsp.h"
 #include "phd_internal.h"
 #include "sharp_plan.h"
+#include "views_plan.h"
 
 namespace phd {
 
@@ -128,7 +129,9 @@ size_t gfft_scratch_elems(const GfftPlan& p, long count);
 bool gfft_run(const GfftPlan& p, const double2* in, double2* out, long count, double2* scr, hipStream_t st);
 
 // ---- per-kernel event timing (opt-in, phd_profile_kernels) -----------------
-enum KernelId { kK1 = 0, kFftRows = 1, kFftCols = 2, kCutoffs = 3, kPalSums = 4, kSharp = 5, kNumKernels = 6 };
+enum KernelId {
+    kK1 = 0, kFftRows = 1, kFftCols = 2, kCutoffs = 3, kPalSums = 4, kSharp = 5, kPack = 6, kNumKernels = 7
+};
 struct KernelProfiler {
     unsigned mask = 0;                              // kernels to bracket with events
     // mask bits 24-30: stride s > 1, only every s-th batch call is bracketed
@@ -223,6 +226,16 @@ struct Context {
     size_t sharp_bytes = 0;
     void* h_sharp = nullptr;
     size_t h_sharp_bytes = 0;
+    // image views (views_plan.h): the packed staging images of one run, the
+    // device table of the pack launch and its pinned copy; ev_views follows
+    // the last pack launch (the table is rewritten only after it)
+    uint8_t* d_vstage = nullptr;
+    size_t vstage_bytes = 0;
+    void* d_views = nullptr;
+    size_t views_bytes = 0;
+    void* h_views = nullptr;
+    size_t h_views_bytes = 0;
+    hipEvent_t ev_views = nullptr;
     hipEvent_t ev[8] = {};
     // two streams per context: `stream` (K1, then the FFT chain) and `tail`
     // (the A-record download, the palette's second pass -- rules upload, Kcut,
@@ -393,6 +406,11 @@ bool run_reports(Context* c, const uint8_t* const* d_imgs, int n, int height, in
 // the context's own buffer (*flat_dev; plan slots must be flat).
 bool enqueue_sharpness(Context* c, const uint8_t* const* d_imgs, int n, int width, const SharpPlan& plan,
                        double* out0, long out_stride, hipStream_t st, double** flat_dev = nullptr);
+// The pack launch of a call's views on st (pack_views.hip): view i goes to
+// dst[i] (3 * height * width bytes; nullptr: the view is left out, as a packed
+// one read in place).  The table goes up through the context's pinned copy;
+// the launch is followed by c->ev_views.  views: validated (view_why).
+bool enqueue_pack_views(Context* c, const phd_image_view* views, uint8_t* const* dst, int n, hipStream_t st);
 // Palette intermediates only (for parity tests).
 bool run_palette_trace(Context* c, const uint8_t* d_img, int height, int width, const phd_config& cfg,
                        std::vector<unsigned>* hist, PaletteDecision* dec,

@@ -398,6 +398,15 @@ hipError_t launch_sharpness_batch(const uint8_t* const* d_imgs, const SharpBox* 
                                   int nboxes, int nslices, int width, const double* k255, SharpPart* d_parts,
                                   double* out0, long out_stride, hipStream_t st, KernelProfiler* prof = nullptr);
 
+// ---- image views (pack_views.hip, pack_view.h) -------------------------------
+// The gather of n views (d_recs: the device table, no packed kind in it) in
+// one launch over (row band, view); max_bands: the most bands of one view.
+// n <= 65535 (grid.y).
+struct PackRec;
+int prof_begin_pack(KernelProfiler* prof, hipStream_t st);
+hipError_t launch_pack_views(const PackRec* d_recs, int n, int max_bands, hipStream_t st,
+                             KernelProfiler* prof = nullptr);
+
 // ---- fp64 planar input of the legacy entry point (planar.hip) ---------------
 struct PlanarSrc {
     const double* r;

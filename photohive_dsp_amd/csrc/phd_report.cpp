@@ -3,6 +3,7 @@
 // Stage order of get_full_report_data (src/interface.c:20-94), per batch of
 // same-size device images on one stream:
 //
+//   K0  gather of non-packed views    views calls only   (pack_views.hip)
 //   K1  hsv/stats/histogram           every image        (palette.hip)
 //   D2H group histograms + moments    -> host decisions  (phd_palette.cpp)
 //   K4  FFT rows, K5 FFT columns      every image        (fft.hip)   || host decides
@@ -131,6 +132,45 @@ bool enqueue_sharpness(Context* c, const uint8_t* const* d_imgs, int n, int widt
     PHD_HIP(launch_sharpness_batch((const uint8_t* const*)ds, (const SharpBox*)(ds + o_box), (const int*)(ds + o_pre),
                                    nb, nslices, width, c->d_k255, (SharpPart*)(ds + up), dst, out0 ? out_stride : 0,
                                    st, &c->prof));
+    return true;
+}
+
+bool enqueue_pack_views(Context* c, const phd_image_view* views, uint8_t* const* dst, int n, hipStream_t st) {
+    std::vector<PackRec> recs;
+    int max_bands = 0;
+    for (int i = 0; i < n; i++) {
+        if (!dst[i]) continue;
+        const PackRec r = pack_record(views[i], dst[i]);
+        recs.push_back(r);
+        max_bands = std::max(max_bands, (r.height + r.band_rows - 1) / r.band_rows);
+    }
+    if (recs.empty()) return true;
+    // the table of the last pack launch is still read until that launch is done
+    // (a caller's stream is not drained by the call that used it)
+    if (!c->ev_views) PHD_HIP(hipEventCreateWithFlags(&c->ev_views, hipEventDisableTiming));
+    else PHD_HIP(hipEventSynchronize(c->ev_views));
+    const size_t bytes = sizeof(PackRec) * recs.size();
+    if (!ensure_device(&c->d_views, &c->views_bytes, bytes)) return false;
+    if (c->h_views_bytes < bytes) {
+        if (c->h_views) (void)hipHostFree(c->h_views);
+        c->h_views = nullptr;
+        c->h_views_bytes = 0;
+        const size_t sz = bytes + bytes / 4 + 4096;
+        if (hipHostMalloc(&c->h_views, sz, hipHostMallocDefault) != hipSuccess) {
+            set_error("hipHostMalloc failed");
+            return false;
+        }
+        c->h_views_bytes = sz;
+    }
+    memcpy(c->h_views, recs.data(), bytes);
+    PHD_HIP(hipMemcpyAsync(c->d_views, c->h_views, bytes, hipMemcpyHostToDevice, st));
+    // (grid.y = view: at most kPackMaxViews a launch)
+    constexpr int kPackMaxViews = 32768;
+    for (size_t k = 0; k < recs.size(); k += kPackMaxViews) {
+        const int m = (int)std::min<size_t>(kPackMaxViews, recs.size() - k);
+        PHD_HIP(launch_pack_views((const PackRec*)c->d_views + k, m, max_bands, st, &c->prof));
+    }
+    PHD_HIP(hipEventRecord(c->ev_views, st));
     return true;
 }
 
@@ -1708,6 +1748,130 @@ extern "C" int phd_report_batch_device_mixed_crops(const uint8_t* const* d_image
     return fails;
 }
 
+// ---- device images as byte-strided views --------------------------------------
+// (the input of get_full_report_data, src/interface.c:20-94, in the layouts GPU
+// producers emit: pack_view.h)
+
+// phd_report_batch_device_mixed_crops over views: the views of a size group
+// that are not packed already are gathered into the lane's staging images by
+// one launch (enqueue_pack_views), then the group runs as any other on the
+// staging pointers and the packed views' own.  run_reports returns with its
+// results on the host, so the staging images are free for the lane's next group.
+extern "C" int phd_report_batch_device_views(const phd_image_view* views, int n_images, const phd_config* cfg,
+                                             const Crop_Boundaries* const* crops, Full_Report_Data** out,
+                                             int* status, void* stream) {
+    clear_error();
+    if (!views || !cfg || !out || !status || n_images <= 0) {
+        set_error("phd_report_batch_device_views: bad arguments");
+        return -1;
+    }
+    // a bad view or bad boxes fail their image alone (the last message stays)
+    std::vector<int> keep;
+    std::string bad;
+    for (int i = 0; i < n_images; i++) {
+        out[i] = nullptr;
+        status[i] = -1;
+        std::string why;
+        if (view_why(views[i], &why) && (!crops || crops_why(crops[i], views[i].height, views[i].width, &why)))
+            keep.push_back(i);
+        else bad = "image " + std::to_string(i) + ": " + why;
+    }
+    Context* c = get_context();
+    if (!c) return -1;
+    if (!bad.empty()) set_error(bad);
+    const int m = (int)keep.size();
+    std::vector<int> hs(m), ws(m);
+    for (int k = 0; k < m; k++) {
+        hs[k] = views[keep[k]].height;
+        ws[k] = views[keep[k]].width;
+    }
+    auto groups = size_groups(hs.data(), ws.data(), m, 64, 64L * 12000000L);
+    // one group of a batch as large as phd_report_batch_device splits: two
+    // groups in its proportion, one per lane
+    if (groups.size() == 1 && m >= 16 && !stream && lanes_setting() >= 2) {
+        const size_t h = ((size_t)m * 131 + 128) / 256;
+        std::vector<int> second(groups[0].begin() + h, groups[0].end());
+        groups[0].resize(h);
+        groups.push_back(std::move(second));
+    }
+    std::atomic<size_t> next{0};
+    if (m > 0)
+        on_lanes(c, groups.size() >= 2 && !stream, [&](Context* cl, int, int) {
+            for (size_t gi; (gi = next.fetch_add(1)) < groups.size();) {
+                const auto& grp = groups[gi];
+                const int gm = (int)grp.size(), height = hs[grp[0]], width = ws[grp[0]];
+                std::vector<phd_image_view> gv(gm);
+                std::vector<const uint8_t*> ptrs(gm);
+                std::vector<uint8_t*> dst(gm, nullptr);
+                std::vector<const Crop_Boundaries*> cr(gm, nullptr);
+                std::vector<Full_Report_Data*> o(gm, nullptr);
+                std::vector<int> st(gm, -1);
+                // staging images at 256-byte steps (K1's aligned form)
+                const size_t step = (3 * (size_t)height * width + 255) & ~(size_t)255;
+                size_t staged = 0;
+                for (int k = 0; k < gm; k++) {
+                    gv[k] = views[keep[grp[k]]];
+                    if (crops) cr[k] = crops[keep[grp[k]]];
+                    staged += pack_kind(width, gv[k].row_stride, gv[k].pixel_stride, gv[k].channel_stride) !=
+                              kPackPacked;
+                }
+                bool ok = staged == 0 || ensure_device((void**)&cl->d_vstage, &cl->vstage_bytes, staged * step);
+                size_t slot = 0;
+                for (int k = 0; k < gm && ok; k++) {
+                    if (pack_kind(width, gv[k].row_stride, gv[k].pixel_stride, gv[k].channel_stride) == kPackPacked) {
+                        ptrs[k] = gv[k].data;
+                    } else {
+                        dst[k] = cl->d_vstage + slot++ * step;
+                        ptrs[k] = dst[k];
+                    }
+                }
+                // (the reference's size checks come first: a size it rejects is not gathered)
+                ok = ok && precheck(height, width) &&
+                     enqueue_pack_views(cl, gv.data(), dst.data(), gm, work_stream(cl, stream));
+                if (ok)
+                    run_reports(cl, ptrs.data(), gm, height, width, *cfg, nullptr, o.data(), st.data(),
+                                (hipStream_t)stream, crops ? cr.data() : nullptr);
+                for (int k = 0; k < gm; k++) {
+                    out[keep[grp[k]]] = o[k];
+                    status[keep[grp[k]]] = st[k];
+                }
+            }
+        });
+    int fails = 0;
+    for (int i = 0; i < n_images; i++) fails += status[i] != 0;
+    return fails;
+}
+
+extern "C" int phd_pack_views_device(const phd_image_view* views, int n_images, uint8_t* const* d_dst, void* stream) {
+    clear_error();
+    if (!views || !d_dst || n_images <= 0) {
+        set_error("phd_pack_views_device: bad arguments");
+        return -1;
+    }
+    for (int i = 0; i < n_images; i++) {
+        std::string why;
+        if (!d_dst[i]) why = "destination is NULL";
+        if (!why.empty() || !view_why(views[i], &why)) {
+            set_error("image " + std::to_string(i) + ": " + why);
+            return -1;
+        }
+    }
+    Context* c = get_context();
+    if (!c) return -1;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const hipStream_t st = work_stream(c, stream);
+    if (!enqueue_pack_views(c, views, d_dst, n_images, st)) return -1;
+    if (!stream) {
+        const hipError_t e = hipStreamSynchronize(st);
+        if (e != hipSuccess) {
+            set_error(std::string("phd_pack_views_device: ") + hipGetErrorString(e));
+            return -1;
+        }
+        c->prof.collect();
+    }
+    return 0;
+}
+
 extern "C" int phd_report_batch_u8_crops(const uint8_t* const* images, const int* heights, const int* widths,
                                          int n_images, const phd_config* cfg, const Crop_Boundaries* const* crops,
                                          Full_Report_Data** out, int* status) {
@@ -1910,6 +2074,9 @@ extern "C" int phd_debug_k1_pixels(const uint8_t* rgb, long n, const phd_config*
     return 0;
 }
 
+// phd_debug_time_kernel's id of K1 without the group histogram (not a profiler slot)
+static constexpr int kTimeStatsPass = 6;
+
 // Micro-benchmark hook: launch one pipeline kernel `iters` times on a device
 // image (after one untimed full report to set up its inputs) and return the
 // average launch time in ms from HIP events.  `ablate` is a debug mask read by
@@ -1948,7 +2115,7 @@ extern "C" int phd_debug_time_kernel(int kernel, const uint8_t* d_rgb, int heigh
     // K1 is timed as the report runs it: fused when the report fuses
     const bool fused = ds <= 1 && fused_palette_ok(gp);
     void* fscratch = nullptr;
-    if (fused || kernel == kNumKernels) {
+    if (fused || kernel == kTimeStatsPass) {
         // the fused K1's group sums and cell counts; the statistics pass's sums of d
         if (hipMalloc(&fscratch, sizeof(double) * 3 * gp.tl + sizeof(unsigned) * HueCells::count(gp) +
                                      256 * sizeof(unsigned long long)) != hipSuccess)
@@ -1981,7 +2148,7 @@ extern "C" int phd_debug_time_kernel(int kernel, const uint8_t* d_rgb, int heigh
         hipError_t e = hipSuccess;
         switch (kernel) {
             case kK1:
-            case kNumKernels:   // K1 without the group histogram (the rgb2hsv + statistics pass)
+            case kTimeStatsPass:   // K1 without the group histogram (the rgb2hsv + statistics pass)
                 e = ds > 1 ? launch_hsv_ds(d_rgb, height, width, ds, gp, cls->fc, cls->d, pd, nchunks, c->d_k255, st)
                            : launch_hsv_stats_batch(d_ptr, 1, height, width, gp, cls->fc, cls->d, pd, 0, 0, nchunks,
                                                     c->d_k255, kernel == kK1, kernel == kK1 && fused,

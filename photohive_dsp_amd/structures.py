@@ -1,7 +1,7 @@
 """ctypes mirrors of the C structs (layouts of /root/reference/structures.py:6-106,
 byte-identical to include/photohive_dsp.h), plus the new phd_config."""
 import ctypes
-from ctypes import POINTER, Structure, c_double, c_float, c_int, c_uint
+from ctypes import POINTER, Structure, c_double, c_float, c_int, c_int64, c_uint, c_void_p
 
 Pixel = c_double
 
@@ -71,3 +71,11 @@ class PhdConfig(Structure):
                 ("quantity_weight", c_float), ("saturation_value_weight", c_float),
                 ("fft_streak_thresh", c_double), ("magnitude_thresh", c_double),
                 ("blur_cutoff_ratio_denom", c_int)]
+
+
+class PhdImageView(Structure):
+    """One device-resident 8-bit image as a byte-strided view (include/photohive_dsp.h:
+    phd_image_view): channel c of pixel (y, x) is the byte at
+    data + y*row_stride + x*pixel_stride + c*channel_stride."""
+    _fields_ = [("data", c_void_p), ("height", c_int), ("width", c_int),
+                ("row_stride", c_int64), ("pixel_stride", c_int64), ("channel_stride", c_int64)]
