@@ -345,6 +345,11 @@ int phd_debug_time_kernel(int kernel, const uint8_t* d_rgb, int height, int widt
 int phd_debug_power_spectrum(const uint8_t* d_rgb, int height, int width, double* d_out);
 /* log_mant, the polar bins' table-driven fp64 log, over n positive device doubles. */
 int phd_debug_log_mant(const double* d_x, double* d_y, long n);
+/* Test hook: n complex transforms of length 3000 (interleaved re, im; device
+ * memory, natural order in and out, unnormalised, e^{-i}) through the
+ * 320-thread column plan whose radix-20 last pass is split over lane pairs
+ * (DESIGN.md section 16), one block each.  0 or -1. */
+int phd_debug_fft_split_pass(const double* d_x, double* d_X, int n);
 /* Host only (no device needed): entries (runs of one polar bin + a sentinel)
  * of the longest spectrum column of this size and bin grid.  Above 256 the
  * compile-time column pass cannot hold the column's list and the size takes

@@ -83,15 +83,6 @@ __device__ __forceinline__ int byte_of(const u32x3a& w, int b) {
     return (x >> (8 * (b & 3))) & 255;
 }
 
-// x of the lane next to this one in its pair (lanes 2m, 2m + 1), by DPP
-// (quad_perm [1, 0, 3, 2])
-__device__ __forceinline__ double dpp_pair_swap(double x) {
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
-    const unsigned lo = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)u, 0xB1, 0xF, 0xF, false);
-    const unsigned hi = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)(u >> 32), 0xB1, 0xF, 0xF, false);
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-
 // The 4 pixels of a 12-byte group rotated by r (0-3) pixels, i.e. its bytes
 // by 3 r = 4 q + sh: pixel e of the result is pixel (e + r) & 3 of w (word i
 // of the result: bytes sh.. of word q + i and the low bytes of word q + i + 1)
@@ -409,7 +400,7 @@ template <int H, int T, bool FULL, int... Rs>
 struct ColK {
     using PL = Plan<H, T, 1, Rs...>;
     using L = typename PL::Last;
-    static constexpr int R = Radices<Rs...>::count > 0 ? H / L::NB : 1;   // last radix
+    static constexpr int R = L::OUT;   // last-pass outputs per thread and round (its radix; half, split)
     static constexpr int NTW = tw_entries<1, Rs...>();
     static constexpr int P = (H + 1) / 2;                                 // row pairs
     static constexpr int CR = (2 * P + T - 1) / T;                        // load rounds
@@ -428,15 +419,27 @@ struct ColK {
     // waves per SIMD of the launch bounds: sized for two resident blocks per
     // CU, one when the column and twiddles fill the LDS
     static constexpr int BPC1 = (int)((160 * 1024) / (sizeof(double2) * (H + NTW) + 1024)) < 2 ? 1 : 2;
-    // (round 6: 3000 rows at 320 threads, three passes, needs three waves per
-    // SIMD for two blocks, i.e. 168 VGPRs: 50-60 spilled; not pursued)
+    // (two blocks of T / 64 waves on four SIMDs: T / 128 rounded up, so 320
+    // threads ask for three waves, 168 VGPRs -- the 3000-row variant whose
+    // last pass is split over lane pairs, phd_internal.h: no spills, but
+    // slower; the counters suggest that its two 5-wave blocks seldom share
+    // a CU)
 #ifdef PHD_COL_MINW3
     // (A/B build: the 3000-row half-prefetch form at three waves per SIMD,
     // three blocks per CU in its 54.2 KB of LDS; 168 VGPRs, ~66 spilled)
-    static constexpr int MINW = (H == 3000 && !FULL) ? 3 : (T >= 512 ? 4 : (T >= 384 ? 3 : 2)) * BPC1 / 2;
+    static constexpr int MINW = (H == 3000 && !FULL) ? 3 : (T > 384 ? 4 : (T > 256 ? 3 : 2)) * BPC1 / 2;
 #else
-    static constexpr int MINW = (T >= 512 ? 4 : (T >= 384 ? 3 : 2)) * BPC1 / 2;
+    static constexpr int MINW = (T > 384 ? 4 : (T > 256 ? 3 : 2)) * BPC1 / 2;
 #endif
+    // The plans at their register limit -- three or more waves per SIMD, and
+    // those with two passes of radix 20 or more (80 data registers each and
+    // their twiddle chains: the 4000- and 6000-row plans, at 244-255 of 256
+    // VGPRs): the column loop recomputes its per-thread addresses at each
+    // stage (fe::opaque) instead of keeping them, which there means in scratch
+    // (21-45 VGPRs spilled with the prime-factor radix 20; 192 VGPRs and none
+    // with this)
+    static constexpr int WIDE = (0 + ... + ((Rs < 0 ? -Rs / 2 : Rs) >= 20 ? 1 : 0));   // passes holding >= 20 values per lane
+    static constexpr bool REMAT = MINW >= 3 || WIDE >= 2;
     // The next column streams into the column buffer by LDS-DMA (no
     // registers) while the current one finishes (round 5).
     //  * Full-prefetch form (PF): p per row gets an LDS array of its own, so
@@ -505,7 +508,11 @@ __global__ __launch_bounds__(T, (ColK<H, T, FULL, Rs...>::MINW)) void k_cols_ct(
     // p per spectrum row: its own array in the full-prefetch form, else the
     // lower half of the column buffer (free once the last pass has read it)
     double* lgb = K::PF ? reinterpret_cast<double*>(rl + kColRunsMax) : reinterpret_cast<double*>(buf);
-    const int tid = threadIdx.x;
+    // (tid0: the thread's index; where K::REMAT, the column loop takes it again
+    // through fe::opaque at each stage, so that no stage's per-thread addresses
+    // and row numbers stay in registers, or scratch, across the others)
+    const int tid0 = threadIdx.x;
+    int tid = tid0;
     // a batch: nimg images of one size, their intermediates, bin sums, max
     // partials and channel sums istride / bstride / fstride / sstride apart;
     // each block runs its columns of every image in turn
@@ -535,12 +542,13 @@ __global__ __launch_bounds__(T, (ColK<H, T, FULL, Rs...>::MINW)) void k_cols_ct(
     // the tiles: element 4p + 2c + r is (row 2p + r, column 2kp + c); a thread
     // loads its column's 32-B half of tiles (row pair tid/2, row tid%2), as raw
     // 16-byte words that land in the registers the LDS stores read
-    const int prow0 = tid / 2, psub = 2 * half + (tid & 1);
     // the column of step u into the buffer by LDS-DMA (PF): element 2 prow0 +
     // (tid & 1) + c T is lane-linear, the wave's base + lane x 16 B
     // part 0: the whole column; 1: its upper half (buffer elements >= H / 2,
     // free while p sits in the lower half), 2: the lower half
     auto dma = [&](int u, int part) {
+        const int tid = opaque<K::REMAT>(tid0);
+        const int prow0 = tid / 2, psub = 2 * half + (tid & 1);
         const u32x4* src = reinterpret_cast<const u32x4*>(inter) + (size_t)prow0 * rs + (size_t)pair_at(u) * 4 + psub;
 #pragma unroll 1
         for (int c = 0; c < K::CR; c++) {
@@ -569,6 +577,7 @@ __global__ __launch_bounds__(T, (ColK<H, T, FULL, Rs...>::MINW)) void k_cols_ct(
     if (u0 < un && !pf_late) dma(u0, 0);
     for (int u = u0; u < un; u++) {
         const int kp = pair_at(u);
+        tid = opaque<K::REMAT>(tid0);
         if (pf_late) dma(u, 0);
         wait_vmem();                              // this wave's DMA of the column is in LDS
         const int col = 2 * (2 * u + (quad >> 1)) + half;
@@ -602,8 +611,9 @@ __global__ __launch_bounds__(T, (ColK<H, T, FULL, Rs...>::MINW)) void k_cols_ct(
             }
             __syncthreads();
         }
-        if (!(ablate & 1)) K::PL::all_but_last(buf, tw, tid);
+        if (!(ablate & 1)) K::PL::template all_but_last<K::REMAT>(buf, tw, tid);
         double2 v[L::ROUNDS][R];
+        tid = opaque<K::REMAT>(tid0);
         if (!(ablate & 16)) {
             L::load(buf, v, tid);
             L::compute(v, tw + K::PL::last_tw_offset, tid);
@@ -617,8 +627,8 @@ __global__ __launch_bounds__(T, (ColK<H, T, FULL, Rs...>::MINW)) void k_cols_ct(
         // lgb: p per spectrum row, 1 for p < 1 (log 0)
 #pragma unroll
         for (int q = 0; q < L::ROUNDS; q++) {
-            const int b = tid + q * T;
-            if (L::active(b) && !(ablate & 16)) {
+            const int b = L::row0(tid, q);          // output k is spectrum row b + k NB
+            if (L::active(tid, q) && !(ablate & 16)) {
 #pragma unroll
                 for (int k = 0; k < R; k++) {
                     const double2 X = v[q][k];
@@ -639,6 +649,7 @@ __global__ __launch_bounds__(T, (ColK<H, T, FULL, Rs...>::MINW)) void k_cols_ct(
         if (u + 1 < un && !pf_late) dma(u + 1, K::PF ? 0 : 1);
         // contiguous runs of one bin: one LDS atomic per run (bins change every
         // few tens of rows along a column; walk_runs)
+        tid = opaque<K::REMAT>(tid0);
         if (!(ablate & 2)) walk_runs<K::E, H % K::E == 0>(lgb, tid * K::E, H, rl, sidx, sl, bscale, lt);
         __syncthreads();
         if (!K::PF && u + 1 < un && !pf_late) dma(u + 1, 2);   // p is read: the lower half too
@@ -766,7 +777,45 @@ __global__ __launch_bounds__(256) void k_log_mant(const double* __restrict__ x, 
     if (i < n) y[i] = log_mant(x[i], lt);
 }
 
+// The split last pass on the device in every build (tests; the default plans
+// do not use it): one 3000-point transform per block with the 320-thread plan
+// 15, 10, split 20 -- the passes, SplitPass's load, twiddles, DPP exchange
+// and the epilogue's indexing of its outputs (active, row0, OUT, NB) as
+// k_cols_ct uses them.  x, X: n transforms of 3000, natural order.
+__global__ __launch_bounds__(320) void k_fft_split_test(const double2* __restrict__ x, const double2* __restrict__ twg,
+                                                        double2* __restrict__ X) {
+    constexpr int N = 3000, T = 320;
+    using PL = Plan<N, T, 1, 15, 10, PHD_SPLIT(20)>;
+    using L = typename PL::Last;
+    constexpr int NTW = tw_entries<1, 15, 10, PHD_SPLIT(20)>();
+    __shared__ __attribute__((aligned(16))) double2 buf[N];
+    __shared__ __attribute__((aligned(16))) double2 tw[NTW];
+    const int tid = threadIdx.x;
+    const size_t base = (size_t)blockIdx.x * N;
+    for (int i = tid; i < N; i += T) buf[i] = x[base + i];
+    for (int i = tid; i < NTW; i += T) tw[i] = twg[i];
+    __syncthreads();
+    PL::template all_but_last<true>(buf, tw, tid);
+    double2 v[L::ROUNDS][L::OUT];
+    L::load(buf, v, tid);
+    L::compute(v, tw + PL::last_tw_offset, tid);
+#pragma unroll
+    for (int q = 0; q < L::ROUNDS; q++) {
+        const int b = L::row0(tid, q);
+        if (L::active(tid, q)) {
+#pragma unroll
+            for (int k = 0; k < L::OUT; k++) X[base + b + k * L::NB] = v[q][k];
+        }
+    }
+}
+
 }  // namespace
+
+hipError_t launch_fft_split_test(const double2* x, const double2* tw, double2* X, int n, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    phd_launch(k_fft_split_test, dim3((unsigned)n), dim3(320), 0, st, x, tw, X);
+    return hipGetLastError();
+}
 
 hipError_t launch_log_mant(const double* x, double* y, long n, hipStream_t st) {
     if (n <= 0) return hipSuccess;
@@ -788,7 +837,10 @@ bool ct_rows_plan(int w, std::vector<int>* radices) {
 bool ct_cols_plan(int h, std::vector<int>* radices) {
 #define PHD_X(N, T, ...)                                       \
     if (h == N) {                                              \
-        if (radices) *radices = std::vector<int>{__VA_ARGS__}; \
+        if (radices) {                                         \
+            *radices = std::vector<int>{__VA_ARGS__};          \
+            for (int& r : *radices) r = std::abs(r);           \
+        }                                                      \
         return true;                                           \
     }
     PHD_CT_COLS(PHD_X)

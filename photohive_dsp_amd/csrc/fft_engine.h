@@ -8,7 +8,9 @@
 // Every size, radix, round count and division is a compile-time constant, so
 // the index arithmetic folds to shifts and multiply-highs.
 //
-// R-point DFTs: 2, 3, 4, 5 and 8 are written out.  Any other R = A*B is a
+// R-point DFTs: 2, 3, 4, 5 and 8 are written out.  Any other R = A*B with
+// coprime A, B (6 10 12 15 20 30) is a prime-factor butterfly (index maps, no
+// twiddles between the A- and B-point stages); the rest (9 16 25 ...) are a
 // small four-step in registers (A-point DFTs over n2, constant twiddles
 // W_R^{n2*k1} from fft_consts.h with +-1 and +-i folded, then B-point DFTs).
 //
@@ -21,6 +23,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
 #include <utility>
 
 #include "fft_consts.h"
@@ -28,27 +31,31 @@
 namespace phd {
 namespace fe {
 
-__device__ __forceinline__ double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ double2 csub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ double2 cmul(double2 a, double2 b) {
+// the butterflies, their constants and index maps also build for the host
+// (tests/native/fft_butterflies.cpp checks them against a direct DFT)
+#define PHD_HD __host__ __device__ __forceinline__
+
+PHD_HD double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
+PHD_HD double2 csub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
+PHD_HD double2 cmul(double2 a, double2 b) {
     return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }
-__device__ __forceinline__ double2 mul_negi(double2 a) { return make_double2(a.y, -a.x); }   // a * (-i)
-__device__ __forceinline__ double2 mul_posi(double2 a) { return make_double2(-a.y, a.x); }   // a * (+i)
+PHD_HD double2 mul_negi(double2 a) { return make_double2(a.y, -a.x); }   // a * (-i)
+PHD_HD double2 mul_posi(double2 a) { return make_double2(-a.y, a.x); }   // a * (+i)
 
 // compile-time for: f(std::integral_constant<int, I>) for I in [0, N)
 template <typename F, int... Is>
-__device__ __forceinline__ void sfor_impl(F&& f, std::integer_sequence<int, Is...>) {
+PHD_HD void sfor_impl(F&& f, std::integer_sequence<int, Is...>) {
     (f(std::integral_constant<int, Is>{}), ...);
 }
 template <int N, typename F>
-__device__ __forceinline__ void sfor(F&& f) {
+PHD_HD void sfor(F&& f) {
     sfor_impl(f, std::make_integer_sequence<int, N>{});
 }
 
 // a * W_R^M, W_R = exp(-2 pi i / R), with the trivial cases folded
 template <int R, int M>
-__device__ __forceinline__ double2 twm(double2 a) {
+PHD_HD double2 twm(double2 a) {
     constexpr int m = M % R;
     constexpr double h = 0.70710678118654752440;
     if constexpr (m == 0) return a;
@@ -66,20 +73,20 @@ __device__ __forceinline__ double2 twm(double2 a) {
 }
 
 template <int R>
-__device__ __forceinline__ void dft(double2 (&v)[R]);
+PHD_HD void dft(double2 (&v)[R]);
 
 template <>
-__device__ __forceinline__ void dft<1>(double2 (&)[1]) {}
+PHD_HD void dft<1>(double2 (&)[1]) {}
 
 template <>
-__device__ __forceinline__ void dft<2>(double2 (&v)[2]) {
+PHD_HD void dft<2>(double2 (&v)[2]) {
     const double2 a = v[0], b = v[1];
     v[0] = cadd(a, b);
     v[1] = csub(a, b);
 }
 
 template <>
-__device__ __forceinline__ void dft<3>(double2 (&v)[3]) {
+PHD_HD void dft<3>(double2 (&v)[3]) {
     constexpr double s1 = 0.86602540378443864676;   // sin(2 pi / 3)
     const double2 t = cadd(v[1], v[2]);
     const double2 d = mul_negi(make_double2(s1 * (v[1].x - v[2].x), s1 * (v[1].y - v[2].y)));
@@ -90,7 +97,7 @@ __device__ __forceinline__ void dft<3>(double2 (&v)[3]) {
 }
 
 template <>
-__device__ __forceinline__ void dft<4>(double2 (&v)[4]) {
+PHD_HD void dft<4>(double2 (&v)[4]) {
     const double2 t0 = cadd(v[0], v[2]), t1 = csub(v[0], v[2]);
     const double2 t2 = cadd(v[1], v[3]), t3 = mul_negi(csub(v[1], v[3]));
     v[0] = cadd(t0, t2);
@@ -100,7 +107,7 @@ __device__ __forceinline__ void dft<4>(double2 (&v)[4]) {
 }
 
 template <>
-__device__ __forceinline__ void dft<5>(double2 (&v)[5]) {
+PHD_HD void dft<5>(double2 (&v)[5]) {
     constexpr double c1 = 0.30901699437494742410;    // cos(2 pi / 5)
     constexpr double c2 = -0.80901699437494742410;   // cos(4 pi / 5)
     constexpr double s1 = 0.95105651629515357212;    // sin(2 pi / 5)
@@ -119,7 +126,7 @@ __device__ __forceinline__ void dft<5>(double2 (&v)[5]) {
 }
 
 template <>
-__device__ __forceinline__ void dft<8>(double2 (&v)[8]) {
+PHD_HD void dft<8>(double2 (&v)[8]) {
     double2 e[4] = {v[0], v[2], v[4], v[6]}, o[4] = {v[1], v[3], v[5], v[7]};
     dft<4>(e);
     dft<4>(o);
@@ -139,7 +146,7 @@ constexpr int split_of(int r) { return (r % 4 == 0 && r > 8) ? 4 : (r % 5 == 0 ?
 // R = A*B: x[B n1 + n2] -> A-point DFTs over n1 (per n2) -> * W_R^{n2 k1}
 // -> B-point DFTs over n2 (per k1) -> X[k1 + A k2]
 template <int A, int B>
-__device__ __forceinline__ void dft_ab(double2 (&v)[A * B]) {
+PHD_HD void dft_ab(double2 (&v)[A * B]) {
     constexpr int R = A * B;
     double2 y[B][A];
     sfor<B>([&](auto n2_) {
@@ -163,9 +170,89 @@ __device__ __forceinline__ void dft_ab(double2 (&v)[A * B]) {
     });
 }
 
+// ---- coprime factors: the prime-factor (Good-Thomas) butterfly ----------------
+// For gcd(A, B) = 1 the index maps n = (B n1 + A n2) mod R on input and
+// k = k1 mod A, k = k2 mod B (the CRT) on output turn W_R^{nk} into
+// W_A^{n1 k1} W_B^{n2 k2}: an A x B two-dimensional DFT with no twiddles
+// between the stages.  Against dft_ab that drops 4 / 8 / 12 non-trivial
+// constant complex products from the radix 10 / 15 / 20 butterflies.
+constexpr int gcd_of(int a, int b) { return b == 0 ? a : gcd_of(b, a % b); }
+template <int A, int B>
+constexpr int pfa_in(int n1, int n2) { return (B * n1 + A * n2) % (A * B); }
+template <int A, int B>
+constexpr int pfa_out(int k1, int k2) {
+    for (int k = 0; k < A * B; k++)
+        if (k % A == k1 && k % B == k2) return k;
+    return -1;
+}
+
+template <int A, int B>
+PHD_HD void dft_pfa(double2 (&v)[A * B]) {
+    static_assert(gcd_of(A, B) == 1, "coprime factors");
+    double2 y[B][A];
+    sfor<B>([&](auto n2_) {
+        constexpr int n2 = decltype(n2_)::value;
+        sfor<A>([&](auto n1_) {
+            constexpr int n1 = decltype(n1_)::value;
+            y[n2][n1] = v[pfa_in<A, B>(n1, n2)];
+        });
+        dft<A>(y[n2]);
+    });
+    sfor<A>([&](auto k1_) {
+        constexpr int k1 = decltype(k1_)::value;
+        double2 z[B];
+        sfor<B>([&](auto n2_) { z[decltype(n2_)::value] = y[decltype(n2_)::value][k1]; });
+        dft<B>(z);
+        sfor<B>([&](auto k2_) { v[pfa_out<A, B>(k1, decltype(k2_)::value)] = z[decltype(k2_)::value]; });
+    });
+}
+
+// (PHD_DFT_PFA=0: an A/B build with the four-step butterflies throughout)
+#ifndef PHD_DFT_PFA
+#define PHD_DFT_PFA 1
+#endif
 template <int R>
-__device__ __forceinline__ void dft(double2 (&v)[R]) {
-    dft_ab<split_of(R), R / split_of(R)>(v);
+PHD_HD void dft(double2 (&v)[R]) {
+    constexpr int A = split_of(R), B = R / A;
+    if constexpr (PHD_DFT_PFA != 0 && gcd_of(A, B) == 1) dft_pfa<A, B>(v);
+    else dft_ab<A, B>(v);
+}
+
+// ---- a butterfly of even radix R = 2 M held by a pair of lanes ----------------
+// Lane h (0 / 1) of the pair holds the (twiddled) inputs 2 j + h, j < M.
+// split_half: their M-point DFT, E[k] (h = 0) or O[k] W_R^k (h = 1).
+// split_join: with the partner's value p for the same k, X[k] = E[k] + O[k] in
+// the even lane and X[k + M] = E[k] - O[k] in the odd lane.
+// split_twiddle: the inter-pass twiddles of lane h's inputs, v[j] *= w^(2j+h)
+// = w^h (w^2)^j, in four interleaved chains as twiddle_powers.
+template <int M>
+PHD_HD void split_twiddle(double2 (&v)[M], const double2 w, int h) {
+    const double2 w2 = cmul(w, w), w4 = cmul(w2, w2), w8 = cmul(w4, w4);
+    double2 p[4];
+    p[0] = make_double2(h ? w.x : 1.0, h ? w.y : 0.0);
+    p[1] = cmul(p[0], w2);
+    p[2] = cmul(p[0], w4);
+    p[3] = cmul(p[1], w4);
+    sfor<M>([&](auto j_) {
+        constexpr int j = decltype(j_)::value;
+        if constexpr (j > 3) p[j & 3] = cmul(p[j & 3], w8);
+        v[j] = cmul(v[j], p[j & 3]);
+    });
+}
+template <int M>
+PHD_HD void split_half(double2 (&v)[M], int h) {
+    dft<M>(v);
+    sfor<M>([&](auto k_) {
+        constexpr int k = decltype(k_)::value;
+        const double2 t = twm<2 * M, k>(v[k]);
+        // (per component: a conditional between the two objects is one between
+        // their addresses, which keeps the whole array in memory)
+        v[k] = make_double2(h ? t.x : v[k].x, h ? t.y : v[k].y);
+    });
+}
+PHD_HD double2 split_join(double2 a, double2 p, int h) {
+    const double s = h ? -1.0 : 1.0;
+    return make_double2(p.x + s * a.x, p.y + s * a.y);
 }
 
 // v[r] *= w^r for r = 1..R-1.  The powers come from four interleaved chains
@@ -196,6 +283,19 @@ __device__ __forceinline__ void twiddle_powers(double2 (&v)[R], const double2 w)
     }
 }
 
+// x again, as a value the compiler cannot tell from a new one: what a loop body
+// derives from it (per-thread LDS addresses, row numbers, lane-parity selects)
+// is computed where it is used instead of once before the loop, where a
+// column kernel at its register limit would keep it in scratch.  ON: the
+// plans at three or more waves per SIMD (ColK::REMAT); the others keep their
+// loop-invariant values in registers (recomputing them cost the 256-thread
+// 3000-row plan 1.3 us per image).
+template <bool ON>
+__device__ __forceinline__ int opaque(int x) {
+    if constexpr (ON) asm volatile("" : "+v"(x));
+    return x;
+}
+
 // ---- one Stockham pass --------------------------------------------------------
 // CLAMP: the lanes past the last butterfly of a partial round load and compute
 // the last butterfly's values (unused, never stored), so v is defined on every
@@ -210,7 +310,12 @@ struct Pass {
     static constexpr bool FULL = NB % T == 0;
     static_assert(N % R == 0, "radix must divide N");
 
+    static constexpr int OUT = R;                    // outputs per thread and round
     __device__ static __forceinline__ bool active(int b) { return FULL || b < NB; }
+    // a last pass's outputs left in registers: round q's live, and the index of
+    // its output 0 (output k: + k NB)
+    __device__ static __forceinline__ bool active(int tid, int q) { return active(tid + q * T); }
+    __device__ static __forceinline__ int row0(int tid, int q) { return tid + q * T; }
     __device__ static __forceinline__ int bfly(int tid, int q) {
         return (FULL || !CLAMP) ? tid + q * T : min(tid + q * T, NB - 1);
     }
@@ -250,11 +355,56 @@ struct Pass {
     }
 };
 
+// x of the lane next to this one in its pair (lanes 2m, 2m + 1), by DPP
+// (quad_perm [1, 0, 3, 2])
+__device__ __forceinline__ double dpp_pair_swap(double x) {
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
+    const unsigned lo = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)u, 0xB1, 0xF, 0xF, false);
+    const unsigned hi = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)(u >> 32), 0xB1, 0xF, 0xF, false);
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+
+// ---- a last pass of even radix R = 2 M split over lane pairs -------------------
+// Lanes 2 b + h hold butterfly b: lane h loads inputs 2 j + h (twiddle
+// w^(2j+h), w = tw[b mod NS]), runs split_half and takes its partner's M
+// values by DPP.  A lane ends with M outputs, k + h M for k < M (element
+// row0() + k NB), in registers the size of a radix-M pass.  One round: 2 NB <= T;
+// the lanes past the last butterfly compute its values (every pair whole).
+template <int N, int T, int R, int NS>
+struct SplitPass {
+    static constexpr int M = R / 2;
+    static constexpr int NB = N / R;
+    static constexpr int ROUNDS = 1;
+    static constexpr int OUT = M;                    // outputs per thread and round
+    static_assert(N % R == 0 && R % 2 == 0, "even radix dividing N");
+    static_assert(2 * NB <= T && T % 2 == 0, "a split pass is one round of lane pairs");
+
+    __device__ static __forceinline__ bool active(int tid, int) { return tid < 2 * NB; }
+    __device__ static __forceinline__ int row0(int tid, int) { return (tid >> 1) + (tid & 1) * M * NB; }
+    __device__ static __forceinline__ int bfly(int tid) { return min(tid >> 1, NB - 1); }
+
+    __device__ static __forceinline__ void load(const double2* buf, double2 (&v)[ROUNDS][M], int tid) {
+        const int b = bfly(tid), h = tid & 1;
+#pragma unroll
+        for (int j = 0; j < M; j++) v[0][j] = buf[b + (2 * j + h) * NB];
+    }
+    __device__ static __forceinline__ void compute(double2 (&v)[ROUNDS][M], const double2* tw, int tid) {
+        const int b = bfly(tid), h = tid & 1;
+        if constexpr (NS > 1) split_twiddle<M>(v[0], tw[b % NS], h);
+        split_half<M>(v[0], h);
+#pragma unroll
+        for (int k = 0; k < M; k++) {
+            const double2 p = make_double2(dpp_pair_swap(v[0][k].x), dpp_pair_swap(v[0][k].y));
+            v[0][k] = split_join(v[0][k], p, h);
+        }
+    }
+};
+
 // ---- plans --------------------------------------------------------------------
 template <int... Rs>
 struct Radices {
     static constexpr int count = sizeof...(Rs);
-    static constexpr int product = (1 * ... * Rs);
+    static constexpr int product = (1 * ... * (Rs < 0 ? -Rs : Rs));   // (PHD_SPLIT radices are negative)
 };
 
 // Twiddle entries a plan needs: sum over passes p >= 1 of NS_p.
@@ -290,21 +440,26 @@ template <int N, int T, int NS, int R, int... Rest>
 struct Plan {
     using Last = typename Plan<N, T, NS * R, Rest...>::Last;
     static constexpr int last_tw_offset = (NS > 1 ? NS : 0) + Plan<N, T, NS * R, Rest...>::last_tw_offset;
-    __device__ static __forceinline__ void all_but_last(double2* buf, const double2* tw, int tid) {
+    template <bool REMAT = false>
+    __device__ static __forceinline__ void all_but_last(double2* buf, const double2* tw, int tid0) {
         using P = Pass<N, T, R, NS, PHD_COL_CLAMP != 0>;
+        const int tid = opaque<REMAT>(tid0);
         double2 v[P::ROUNDS][R];
         P::load(buf, v, tid);
         P::compute(v, tw, tid);
         __syncthreads();
         P::store(buf, v, tid);
         __syncthreads();
-        Plan<N, T, NS * R, Rest...>::all_but_last(buf, tw + (NS > 1 ? NS : 0), tid);
+        Plan<N, T, NS * R, Rest...>::template all_but_last<REMAT>(buf, tw + (NS > 1 ? NS : 0), tid0);
     }
 };
+// (a negative last radix, PHD_SPLIT(R) in the plan tables: that pass split over
+// lane pairs, SplitPass)
 template <int N, int T, int NS, int R>
 struct Plan<N, T, NS, R> {
-    using Last = Pass<N, T, R, NS, PHD_COL_CLAMP != 0>;
+    using Last = std::conditional_t<(R < 0), SplitPass<N, T, (R < 0 ? -R : 2), NS>, Pass<N, T, (R < 0 ? 1 : R), NS, PHD_COL_CLAMP != 0>>;
     static constexpr int last_tw_offset = 0;
+    template <bool REMAT = false>
     __device__ static __forceinline__ void all_but_last(double2*, const double2*, int) {}
 };
 

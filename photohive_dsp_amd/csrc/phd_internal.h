@@ -302,8 +302,14 @@ int fft_cols_blocks(int height, int wf, int nbins, const FftPlan& plan, size_t* 
     X(640, 128, 5, 8, 16)        \
     X(480, 128, 5, 6, 16)        \
     X(512, 64, 8, 8, 8)
-// (the 3000-row plan's threads and radices are overridable for A/B builds:
-// make variant VFLAGS="-DPHD_C3000_T=320 -DPHD_C3000_R=20,15,10")
+// A last column radix written PHD_SPLIT(R), R even: each butterfly of that pass
+// is held by two adjacent lanes (fe::SplitPass), R / 2 values per lane.
+#define PHD_SPLIT(R) (-(R))
+// (the 3000-row plan's threads and radices are overridable for A/B builds.
+// Measured and not kept, DESIGN.md section 16: 320 threads with the last pass
+// split -- 200, 300 and 2 x 150 lanes, one round per pass, 145 VGPRs, no
+// spills -- ran 66 us against 47 us per column pass:
+// make -C photohive_dsp_amd/csrc variant V=c320 VFLAGS="-DPHD_C3000_T=320 -DPHD_C3000_R=15,10,-20")
 #ifndef PHD_C3000_T
 #define PHD_C3000_T 256
 #endif
@@ -356,6 +362,10 @@ size_t fft_cols_ct_lds(int height);
 int fft_cols_ct_threads(int height);
 // log_mant (phd_device.h) over n positive doubles (tests)
 hipError_t launch_log_mant(const double* x, double* y, long n, hipStream_t st);
+// n 3000-point transforms, one per block, through the 320-thread plan with the
+// split last pass (tests: fe::SplitPass on the device in every build); tw: the
+// 3000-row column plan's twiddles (get_ct_twiddles)
+hipError_t launch_fft_split_test(const double2* x, const double2* tw, double2* X, int n, hipStream_t st);
 // persistent grid of the column kernel (= entries of fmax_part)
 int fft_cols_ct_blocks(int height);
 // tw: the plan's per-pass tables W_{NS*R}^jm (jm < NS) for passes 1.. (host built).

@@ -2194,6 +2194,24 @@ extern "C" int phd_debug_log_mant(const double* d_x, double* d_y, long n) {
 }
 
 
+extern "C" int phd_debug_fft_split_pass(const double* d_x, double* d_X, int n) {
+    clear_error();
+    Context* c = get_context();
+    if (!c || !d_x || !d_X || n < 1) return -1;
+    std::lock_guard<std::mutex> lk(c->mu);
+    // the 3000-row column plan's tables: W_150^jm and W_3000^jm, whatever its last pass's form
+    const double2* tw = get_ct_twiddles(c, 3000, false);
+    if (!tw) return -1;
+    hipError_t e = launch_fft_split_test(reinterpret_cast<const double2*>(d_x), tw, reinterpret_cast<double2*>(d_X), n,
+                                         c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        set_error(std::string("phd_debug_fft_split_pass: ") + hipGetErrorString(e));
+        return -1;
+    }
+    return 0;
+}
+
 extern "C" int phd_debug_power_spectrum(const uint8_t* d_rgb, int height, int width, double* d_out) {
     clear_error();
     Context* c = get_context();

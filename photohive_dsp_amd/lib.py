@@ -133,6 +133,7 @@ lib.phd_free_pgm.argtypes = [P(Image_PGM)]
 # older build through PHD_LIB (tools/); the shipped library exports all of them
 # (tests/test_abi.py checks every symbol of include/photohive_dsp.h)
 for _name, _res, _args in (("phd_shutdown", None, []),
+                           ("phd_debug_fft_split_pass", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
                            ("phd_install_crash_maps", ctypes.c_int, [ctypes.c_char_p]),
                            ("phd_debug_library_threads", ctypes.c_int, [ctypes.c_int]),
                            ("phd_debug_legacy_report", P(Full_Report_Data),
