@@ -16,6 +16,7 @@
 
 #include "../../include/photohive_dsp.h"
 #include "phd_internal.h"
+#include "batch_plan.h"
 #include "sharp_plan.h"
 #include "views_plan.h"
 
@@ -307,6 +308,9 @@ int lanes_setting();
 // buffers a caller (or PyTorch's default stream) is still producing are
 // complete before the library reads them.
 hipStream_t work_stream(Context* c, void* stream);
+// workspace records start at 256-byte steps
+constexpr size_t kAlign = 256;
+inline size_t al(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
 bool ensure_device(void** p, size_t* cap, size_t need);
 bool ensure_pinned(Context* c, size_t need);
 const FftPlanHost* get_plan(Context* c, int n, bool composite = false);
@@ -378,6 +382,11 @@ Full_Report_Data* assemble(const RGB_Statistics& st, double s_bar, const Palette
                            const double* pal, long n_hsv, const BlurTable& tbl, const unsigned long long* bin_sums,
                            double fmax, const phd_config& cfg, const Crop_Boundaries* crops,
                            const double* sharp_sums, std::string* why, double bscale = 0.0);
+// The blur half of assemble alone (phd_blur_batch_device): flat is na x nr.
+void finish_blur(const BlurTable& tbl, const unsigned long long* bin_sums, double fmax, const phd_config& cfg,
+                 double* flat, Blur_Vector* vectors, double bscale = 0.0);
+RGB_Statistics stats_from_sums(const unsigned long long* m, long n);   // from K1's six moments of n pixels
+bool all_aligned(const uint8_t* const* p, int n);                      // every pointer 4-byte aligned
 // get_full_report_data's reports in the reference's allocation shape
 // (phd_legacy.cpp): a separately malloc'd copy, its registration as a live
 // tree, and its release (false when r is not a live tree)
@@ -389,9 +398,6 @@ bool legacy_release(Full_Report_Data* r);
 // RGB8 pipeline when every value is k/255.0, else the fp64 planar kernels.
 Full_Report_Data* report_planar(Context* c, const double* r, const double* g, const double* b, int height,
                                 int width, const phd_config& cfg, const Crop_Boundaries* crops);
-struct ImageIn {
-    const uint8_t* d_img;   // device RGB8, rows of 3*width bytes
-};
 // Run the full report on n same-size device images.  out[i]/status[i] per image.
 // crops: one set of boxes for every image (the single-image entries; two
 // launches per box, sharpness.hip's k_sharp_pass).  img_crops (crops must be

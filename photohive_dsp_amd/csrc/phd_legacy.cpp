@@ -10,7 +10,7 @@
 // (free_blur_vector_group, src/blur_profile.c:481-484) and the sharpnesses
 // (src/interface.c:103-106).  A C caller may therefore free() any member
 // itself.  The batch entry points keep one pooled block per report
-// (phd_report.cpp, assemble); the legacy entry copies that block into such a
+// (phd_assemble.cpp, assemble); the legacy entry copies that block into such a
 // tree, and free_full_report (src/interface.c:97-111) frees a tree member by
 // member.  Host-only C++ (no HIP), so tests/test_legacy_tree.py builds it
 // with a sanitiser on the CPU.

@@ -22,9 +22,6 @@ namespace phd {
 
 namespace {
 
-constexpr size_t kAl = 256;
-size_t al(size_t x) { return (x + kAl - 1) / kAl * kAl; }
-
 // device / pinned-free host records of one planar call
 struct PRec {
     size_t flags, avg, lrng, part1, part2, hist, spart, chunk, rules, search, off, pal, bins, fmax, sharp, total;
@@ -92,7 +89,7 @@ Full_Report_Data* report_planar(Context* c, const double* r, const double* g, co
     const int nchunks = (int)((n_hsv + kChunk - 1) / kChunk);
     const int nbins = cfg.radius_partitions * cfg.angle_partitions, wf = width / 2 + 1;
     const int ncrops = crops ? crops->N : 0;
-    if (!ensure_device(&c->d_prec, &c->prec_bytes, kAl)) return nullptr;
+    if (!ensure_device(&c->d_prec, &c->prec_bytes, kAlign)) return nullptr;
     int* flags = (int*)c->d_prec;
     PHD_HIPN(hipMemsetAsync(flags, 0, sizeof(int), st));
     PHD_HIPN(hipMemcpyAsync((void*)P.r, r, sizeof(double) * n, hipMemcpyHostToDevice, st));

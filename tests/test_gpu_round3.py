@@ -39,7 +39,7 @@ def test_log_mant_matches_host_log():
 
 def test_mixed_batch_groups_past_64_images():
     """phd_report_batch_device_mixed runs small sizes in groups larger than 64
-    (pixel budget, phd_report.cpp size_groups): 70 images of 352x352 between
+    (pixel budget, batch_plan.h size_groups): 70 images of 352x352 between
     three of 400x400, every report equal to its single-image device report."""
     L, torch = _lib()
     from photohive_dsp_amd import synth
