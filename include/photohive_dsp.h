@@ -295,6 +295,74 @@ int phd_pack_views_device(const phd_image_view* views, int n_images, uint8_t* co
  * dst[3*height*width].  0 or -1. */
 int phd_debug_pack_view_host(const phd_image_view* view, uint8_t* dst);
 
+/* ---- device images of any element type ---------------------------------------
+ * The reference's pixel is a double (typedef double Pixel, src/types.h:5) and
+ * get_full_report_data (src/interface.c:20-94) reports on whatever doubles it
+ * is given; the device calls above take 8-bit images only.  A typed view
+ * describes 8- or 16-bit integers, halves, floats or doubles at byte strides:
+ * a 10-, 12- or 16-bit decode, a float CHW tensor in 0..1, double planes that
+ * are on the GPU already. */
+enum { PHD_ELEM_U8 = 0, PHD_ELEM_U16 = 1, PHD_ELEM_F16 = 2, PHD_ELEM_F32 = 3, PHD_ELEM_F64 = 4 };
+enum { PHD_VIEW_SNAP_U8 = 1 };
+
+/* One device-resident image as a byte-strided view of typed elements: channel
+ * c of pixel (y, x) is the element at
+ *   data + y*row_stride + x*pixel_stride + c*channel_stride   (BYTES),
+ * and its value -- the reference's Pixel -- is (double)element / max_value
+ * (max_value 0: the type's own, 255 for U8, 65535 for U16, 1.0 for the float
+ * types; 1023.0 for a 10-bit image in 16-bit storage, 255.0 for floats in
+ * 0..255).  The widening is exact and the division is IEEE fp64 division.  NaN
+ * and infinity stay what they are and are rejected where the legacy entry
+ * rejects them.
+ * Valid: the rules of phd_image_view, and elem one of PHD_ELEM_*, data and the
+ * three strides multiples of the element size (every access naturally
+ * aligned), max_value 0 or finite and > 0, no unknown bit in flags.
+ * An image is 8-bit when every value equals (double)j / 255.0 for an integer j
+ * in 0..255 (the rule of the legacy entry's planar doubles, utils.py:30-46);
+ * 16-bit values that are all multiples of 257 qualify.
+ * PHD_VIEW_SNAP_U8 (F16 and F32 views at the default maximum; ignored for the
+ * others): an element also counts as 8-bit value j when it equals the type's
+ * round-to-nearest value of j / 255, (T)((double)j / 255.0) -- what a uint8
+ * image divided by 255 in that type holds.  Without it such a float image is
+ * reported as the doubles its floats widen to. */
+typedef struct phd_typed_view {
+    const void* data;            /* element of channel R of pixel (0,0) */
+    int height, width;
+    int64_t row_stride, pixel_stride, channel_stride;   /* BYTES, as phd_image_view; may be negative or 0 */
+    int elem;                    /* PHD_ELEM_* */
+    int flags;                   /* PHD_VIEW_SNAP_U8 or 0 */
+    double max_value;            /* 0 = the type's: 255, 65535, 1.0 */
+} phd_typed_view;
+
+/* phd_report_batch_device_views over typed views (get_full_report_data,
+ * src/interface.c:20-94, per image on the Pixels of src/types.h:5): the same
+ * semantics, return values and per-image failure rules; any sizes, boxes in
+ * view coordinates, no byte read outside a view's span.  8-bit images (the rule
+ * above) join the RGB8 run of their size group, with its results bit for bit;
+ * a PHD_ELEM_U8 view at the default maximum is routed exactly as
+ * phd_report_batch_device_views routes it (a packed one is read in place).
+ * Every other image is decoded into double planes on the device and takes the
+ * fp64 pipeline of get_full_report_data, one image at a time.  A non-finite
+ * image fails alone. */
+int phd_report_batch_device_typed_views(const phd_typed_view* views, int n_images, const phd_config* cfg,
+                                        const Crop_Boundaries* const* crops, Full_Report_Data** out, int* status,
+                                        void* stream);
+
+/* The decode alone (the planes of Image_RGB, src/image_processing.h:31-36, as
+ * Pixels, src/types.h:5): d_planes[i] (device) receives 3*height*width
+ * doubles, the R plane, then G, then B; any size from 1x1.  Enqueued on
+ * `stream`, or (NULL) on the library's stream and waited for.  A bad view
+ * fails the call.  0 or -1. */
+int phd_decode_views_device(const phd_typed_view* views, int n_images, double* const* d_planes, void* stream);
+
+/* Validation hook, host only (no GPU): the decode kernels' row code
+ * (decode_view.h; the reference reads its planes per pixel,
+ * src/image_processing.c:387) over one view of host memory.  planes
+ * [3*height*width], rgb8 [3*height*width] (j = rint(value * 255), or NULL)
+ * and *is_u8 (1 when the image is 8-bit by the rule above, snap included; or
+ * NULL).  0, or -1 with phd_last_error. */
+int phd_debug_decode_view_host(const phd_typed_view* view, double* planes, uint8_t* rgb8, int* is_u8);
+
 /* Palette intermediates of one device-resident image, for bit-exact checks:
  * hist[TL] (arm_octree quantities), parents[*n_parents] (valid_parents in
  * palette order), kept[*n_parents] (pixels surviving group_irregular_pixels).
@@ -393,7 +461,7 @@ int phd_last_timings(double* ms, int n);
 /* Per-kernel GPU time from HIP events recorded on the launch stream around
  * every launch of the kernels in `mask` (bit k = kernel k: 0 hsv_stats,
  * 1 fft_rows, 2 fft_cols, 3 palette_cutoffs, 4 palette_sums, 5 sharpness,
- * 6 pack_views).
+ * 6 pack_views, 7 classify_views, 8 decode_views).
  * phd_profile_kernels resets the counters; phd_profile_read returns the
  * accumulated milliseconds and launch count of one kernel. */
 int phd_profile_kernels(unsigned mask);

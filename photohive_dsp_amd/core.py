@@ -18,7 +18,9 @@ from types import SimpleNamespace
 import numpy as np
 
 from .lib import last_error, lib
-from .structures import Crop_Boundaries, Full_Report_Data, PhdConfig, PhdImageView, Pixel_HSV, RGB_Statistics
+from .structures import (PHD_ELEM_F16, PHD_ELEM_F32, PHD_ELEM_F64, PHD_ELEM_U8, PHD_ELEM_U16, PHD_VIEW_SNAP_U8,
+                         Crop_Boundaries, Full_Report_Data, PhdConfig, PhdImageView, PhdTypedView, Pixel_HSV,
+                         RGB_Statistics)
 from .utils import hsv_to_rgb, image_pgm_to_pillow, to_rgb8
 
 DEFAULTS = dict(h_partitions=18, s_partitions=2, v_partitions=3, black_thresh=0.1, gray_thresh=0.1,
@@ -361,6 +363,115 @@ def pack_views_device(images, layout="HWC", bgr=False, stream=None):
     dst = (ctypes.c_void_p * n)(*[o.data_ptr() for o in out])
     if lib.phd_pack_views_device(views, n, dst, _stream_handle(stream)) != 0:
         raise RuntimeError(f"pack_views_device failed: {last_error()}")
+    return out
+
+
+def _typed_elems():
+    import torch
+    elems = {torch.uint8: PHD_ELEM_U8, torch.float16: PHD_ELEM_F16, torch.float32: PHD_ELEM_F32,
+             torch.float64: PHD_ELEM_F64}
+    if hasattr(torch, "uint16"):
+        elems[torch.uint16] = PHD_ELEM_U16
+    return elems
+
+
+def make_typed_views(tensors, layout="HWC", bgr=False, max_value=None, snap_u8=False):
+    """The PhdTypedView descriptors of uint8, uint16, float16, float32 or
+    float64 torch tensors, with no copy: make_views' layouts ([H, W, C] with
+    C = 3 or 4, or [C, H, W]; any strides; one 4-D tensor as its images;
+    bgr=True reverses the channels), byte strides = element strides *
+    element_size().  16-bit images held as int16 go in as
+    t.view(torch.uint16).  An element's value is element / max_value
+    (None: the type's own 255, 65535 or 1.0; a number, or one per image:
+    1023 for 10-bit data in 16-bit storage, 255 for floats in 0..255).
+    snap_u8 (a bool, or one per image): float16 / float32 elements that are
+    uint8 / 255 rounded to that type count as that 8-bit value, so a
+    ToTensor() image gets the report of the 8-bit image it came from.  An entry
+    that is a PhdTypedView already is taken as it is.  Needs no GPU (CPU tensors
+    work).  Returns (array of PhdTypedView, objects to keep alive)."""
+    import torch
+    if layout not in ("HWC", "CHW"):
+        raise ValueError(f"layout must be 'HWC' or 'CHW', not {layout!r}")
+    if isinstance(tensors, torch.Tensor):
+        if tensors.dim() != 4:
+            raise ValueError("a single tensor must be 4-D (a batch of images)")
+        tensors = list(tensors.unbind(0))
+    tensors = list(tensors)
+    n = len(tensors)
+    maxes = list(max_value) if isinstance(max_value, (list, tuple)) else [max_value] * n
+    snaps = list(snap_u8) if isinstance(snap_u8, (list, tuple)) else [snap_u8] * n
+    if len(maxes) != n or len(snaps) != n:
+        raise ValueError(f"max_value / snap_u8 must be one value or one per image ({n} images)")
+    elems = _typed_elems()
+    views = (PhdTypedView * max(1, n))()
+    for i, t in enumerate(tensors):
+        if isinstance(t, PhdTypedView):
+            views[i] = t
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype not in elems:
+            raise ValueError(f"image {i}: expected a uint8, uint16, float16, float32 or float64 torch tensor")
+        if t.dim() != 3:
+            raise ValueError(f"image {i}: expected 3 dimensions ({layout}), got {t.dim()}")
+        if layout == "HWC":
+            (h, w, ch), (rs, ps, cs) = t.shape, t.stride()
+        else:
+            (ch, h, w), (cs, rs, ps) = t.shape, t.stride()
+        if ch not in (3, 4):
+            raise ValueError(f"image {i}: expected 3 or 4 channels, got {ch}")
+        es = t.element_size()
+        rs, ps, cs = rs * es, ps * es, cs * es
+        data = t.data_ptr()
+        if bgr:
+            data, cs = data + 2 * cs, -cs
+        mv = 0.0 if maxes[i] is None else float(maxes[i])
+        if not (mv >= 0.0 and mv != float("inf")) or (maxes[i] is not None and mv == 0.0):
+            raise ValueError(f"image {i}: max_value must be finite and positive")
+        views[i] = PhdTypedView(data, int(h), int(w), int(rs), int(ps), int(cs), elems[t.dtype],
+                                PHD_VIEW_SNAP_U8 if snaps[i] else 0, mv)
+    return views, tensors
+
+
+def reports_device_typed(images, layout="HWC", bgr=False, max_value=None, snap_u8=False, stream=None,
+                         salient_characters=None, **kw):
+    """Reports for device tensors of any element type in any byte-strided layout
+    (make_typed_views; any sizes): a 16-bit decode, a float CHW tensor in 0..1,
+    double planes already on the GPU.  Images whose values are exactly 8-bit
+    (j / 255; with snap_u8 also floats that are uint8 / 255 in their own type)
+    join the RGB8 batch of their size and get its report bit for bit; every
+    other image is decoded to doubles on the device and reported by the fp64
+    pipeline of get_full_report_data on those doubles, with no host round trip
+    of pixels (phd_report_batch_device_typed_views).  salient_characters:
+    per-image crop boxes in each view's own coordinates (normalize_salient)."""
+    views, keep = make_typed_views(images, layout, bgr, max_value, snap_u8)
+    n = len(keep)
+    cfg = make_config(**kw)
+    crops = normalize_salient(salient_characters, n)
+    outs = (POINTER(Full_Report_Data) * n)()
+    st = (ctypes.c_int * n)()
+    s = _stream_handle(stream)
+    lib.phd_report_batch_device_typed_views(views, n, ctypes.byref(cfg), crops[0] if crops else None, outs, st, s)
+    res = [(_finish(outs[i], views[i].height, views[i].width, kw) if st[i] == 0 else None) for i in range(n)]
+    if any(r is None for r in res):
+        err = last_error()
+        del res                     # (the reports that did come back are freed)
+        raise RuntimeError(f"reports_device_typed failed: {err}")
+    return res
+
+
+def decode_views_device(images, layout="HWC", bgr=False, max_value=None, stream=None):
+    """The decode alone (phd_decode_views_device): float64 [3, H, W] device
+    tensors holding element / max_value of the given views (make_typed_views),
+    the planes get_full_report_data takes."""
+    import torch
+    views, keep = make_typed_views(images, layout, bgr, max_value)
+    n = len(keep)
+    if n == 0:
+        return []
+    out = [torch.empty((3, views[i].height, views[i].width), dtype=torch.float64,
+                       device=keep[i].device if isinstance(keep[i], torch.Tensor) else "cuda") for i in range(n)]
+    dst = (ctypes.c_void_p * n)(*[o.data_ptr() for o in out])
+    if lib.phd_decode_views_device(views, n, dst, _stream_handle(stream)) != 0:
+        raise RuntimeError(f"decode_views_device failed: {last_error()}")
     return out
 
 

@@ -574,6 +574,7 @@ void destroy_context(Context* c) {
     c->h_sharp = nullptr;
     dfree(c->d_vstage);
     dfree(c->d_views);
+    dfree(c->d_snap);
     if (c->h_views) (void)hipHostFree(c->h_views);
     c->h_views = nullptr;
     ev_destroy(c->ev_views);
@@ -651,6 +652,7 @@ void KernelProfiler::end(int slot, hipStream_t st) {
 
 int prof_begin_sharp(KernelProfiler* prof, hipStream_t st) { return prof ? prof->begin(kSharp, st) : -1; }
 int prof_begin_pack(KernelProfiler* prof, hipStream_t st) { return prof ? prof->begin(kPack, st) : -1; }
+int prof_begin_kernel(KernelProfiler* prof, int kernel, hipStream_t st) { return prof ? prof->begin(kernel, st) : -1; }
 void prof_end(KernelProfiler* prof, int slot, hipStream_t st) {
     if (prof) prof->end(slot, st);
 }

@@ -319,3 +319,12 @@ extern "C" int phd_debug_power_spectrum(const uint8_t* d_rgb, int height, int wi
     }
     return 0;
 }
+
+// The decode kernels' host twin (phd_views.cpp: decode_view_host) behind the C ABI.
+extern "C" int phd_debug_decode_view_host(const phd_typed_view* view, double* planes, uint8_t* rgb8, int* is_u8) {
+    clear_error();
+    std::string why;
+    const int rc = decode_view_host(view, planes, rgb8, is_u8, &why);
+    if (rc != 0) set_error(why);
+    return rc;
+}

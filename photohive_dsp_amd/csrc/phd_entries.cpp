@@ -711,6 +711,190 @@ extern "C" int phd_pack_views_device(const phd_image_view* views, int n_images, 
     return 0;
 }
 
+// ---- typed views ---------------------------------------------------------------
+// One same-size group of a typed call on a lane.  tv[k]: the typed view of
+// imgs[k].  The classifier writes every non-U8 view's RGB8 image into the
+// lane's staging area and says which are 8-bit; those, with the U8 views
+// (gathered by the pack launch unless packed), are one run_reports call; each
+// other finite image is decoded into the lane's double planes and reported by
+// the fp64 planar pipeline (phd_planar.cpp), one at a time.
+static void run_typed_group(Context* cl, const std::vector<BatchImage>& imgs, const phd_typed_view* const* tv,
+                            const std::vector<int>& grp, bool boxes, const phd_config& cfg, void* stream,
+                            RunResults* r) {
+    const int gm = (int)grp.size(), height = imgs[grp[0]].height, width = imgs[grp[0]].width;
+    // (the reference's size checks come first: a size it rejects is not read)
+    if (!precheck(height, width)) {
+        set_error("image " + std::to_string(imgs[grp[gm - 1]].index) + ": " + phd_last_error());
+        return;
+    }
+    const hipStream_t st = work_stream(cl, stream);
+    const size_t step = (3 * (size_t)height * width + 255) & ~(size_t)255;
+    std::vector<phd_image_view> gv(gm);
+    std::vector<uint8_t*> pack_dst(gm, nullptr), cls_dst;
+    std::vector<phd_typed_view> cls_views;
+    std::vector<int> cls_k;                                   // the group's classified images
+    size_t staged = 0;
+    for (int k = 0; k < gm; k++) {
+        const phd_typed_view& v = *tv[grp[k]];
+        gv[k] = typed_as_u8_view(v);
+        if (!typed_is_u8_view(v)) cls_k.push_back(k);
+        staged += !typed_is_u8_view(v) ||
+                  pack_kind(width, gv[k].row_stride, gv[k].pixel_stride, gv[k].channel_stride) != kPackPacked;
+    }
+    // every allocation before the first launch that writes into it
+    const size_t n = (size_t)height * width;
+    if (staged && !ensure_device((void**)&cl->d_vstage, &cl->vstage_bytes, staged * step)) return;
+    std::vector<const uint8_t*> ptrs(gm, nullptr);
+    size_t slot = 0;
+    for (int k = 0; k < gm; k++) {
+        const bool u8 = typed_is_u8_view(*tv[grp[k]]);
+        if (u8 && pack_kind(width, gv[k].row_stride, gv[k].pixel_stride, gv[k].channel_stride) == kPackPacked) {
+            ptrs[k] = gv[k].data;
+            continue;
+        }
+        uint8_t* d = cl->d_vstage + slot++ * step;
+        ptrs[k] = d;
+        if (u8) pack_dst[k] = d;
+        else {
+            cls_dst.push_back(d);
+            cls_views.push_back(*tv[grp[k]]);
+        }
+    }
+    std::vector<int> flags(cls_k.size(), 0);
+    if (!classify_views(cl, cls_views.data(), cls_dst.data(), (int)cls_k.size(), st, flags.data())) return;
+    if (!enqueue_pack_views(cl, gv.data(), pack_dst.data(), gm, st)) return;
+    std::vector<int> route(gm, 0);                            // 0: RGB8 run, else the classifier's flags
+    for (size_t q = 0; q < cls_k.size(); q++) route[cls_k[q]] = flags[q];
+    // the RGB8 run
+    std::vector<int> run_k;
+    for (int k = 0; k < gm; k++)
+        if (!route[k]) run_k.push_back(k);
+    if (!run_k.empty()) {
+        const int m = (int)run_k.size();
+        std::vector<const uint8_t*> rp(m);
+        std::vector<const Crop_Boundaries*> cr(m);
+        for (int q = 0; q < m; q++) {
+            rp[q] = ptrs[run_k[q]];
+            cr[q] = imgs[grp[run_k[q]]].boxes;
+        }
+        RunResults rr(m);
+        run_reports(cl, rp.data(), m, height, width, cfg, nullptr, rr.o.data(), rr.st.data(), (hipStream_t)stream,
+                    boxes ? cr.data() : nullptr);
+        for (int q = 0; q < m; q++) {
+            r->o[run_k[q]] = rr.o[q];
+            r->st[run_k[q]] = rr.st[q];
+        }
+    }
+    // the fp64 images, one at a time; a failing image keeps its message (the last one stays)
+    std::string bad, why;
+    for (int k = 0; k < gm; k++) {
+        if (!route[k]) continue;
+        const std::string name = "image " + std::to_string(imgs[grp[k]].index) + ": ";
+        if (route[k] & kDecNonFinite) {
+            bad = name + "Error: channel values must be finite (NaN or infinity in the image).";
+            continue;
+        }
+        if (!validate_config(cfg, &why)) {
+            bad = name + why;
+            continue;
+        }
+        // (the stream is idle: the planes may move)
+        if (!ensure_device((void**)&cl->d_planes, &cl->planes_bytes, sizeof(double) * 4 * n)) {
+            bad = name + phd_last_error();
+            continue;
+        }
+        double* dp = cl->d_planes;
+        Full_Report_Data* o = nullptr;
+        if (enqueue_decode_view(cl, *tv[grp[k]], dp, st))
+            o = report_planes_device(cl, PlanarSrc{dp, dp + n, dp + 2 * n}, height, width, cfg,
+                                     boxes ? imgs[grp[k]].boxes : nullptr, st);
+        (void)hipStreamSynchronize(st);
+        cl->prof.collect();
+        if (o) {
+            r->o[k] = o;
+            r->st[k] = 0;
+        } else bad = name + phd_last_error();
+    }
+    if (!bad.empty()) set_error(bad);
+}
+
+// Device images of any element type as byte-strided views (the input of
+// get_full_report_data, src/interface.c:20-94, as the reference's Pixels,
+// src/types.h:5): the views call over typed views.
+extern "C" int phd_report_batch_device_typed_views(const phd_typed_view* views, int n_images, const phd_config* cfg,
+                                                   const Crop_Boundaries* const* crops, Full_Report_Data** out,
+                                                   int* status, void* stream) {
+    clear_error();
+    if (!views || !cfg || !out || !status || n_images <= 0) {
+        set_error("phd_report_batch_device_typed_views: bad arguments");
+        return -1;
+    }
+    // a bad view or bad boxes fail their image alone (the last message stays)
+    std::vector<BatchImage> imgs;
+    std::vector<const phd_typed_view*> tv;
+    std::string bad;
+    for (int i = 0; i < n_images; i++) {
+        out[i] = nullptr;
+        status[i] = -1;
+        std::string why;
+        if (typed_view_why(views[i], &why) &&
+            (!crops || crops_why(crops[i], views[i].height, views[i].width, &why))) {
+            imgs.push_back({i, nullptr, nullptr, views[i].height, views[i].width, crops ? crops[i] : nullptr});
+            tv.push_back(&views[i]);
+        } else bad = "image " + std::to_string(i) + ": " + why;
+    }
+    Context* c = get_context();
+    if (!c) return -1;
+    if (!bad.empty()) set_error(bad);
+    auto groups = mixed_groups(imgs);
+    split_for_lanes(&groups, stream);
+    std::atomic<size_t> taken{0};                             // groups taken past each lane's first
+    if (!groups.empty())
+        on_lanes(c, groups.size() >= 2 && !stream, [&](Context* cl, int lane, int nl) {
+            for (size_t gi = lane; gi < groups.size(); gi = nl + taken.fetch_add(1)) {
+                const std::vector<int>& grp = groups[gi];
+                RunResults r(grp.size());
+                std::vector<int> idx(grp.size());
+                for (size_t k = 0; k < grp.size(); k++) idx[k] = imgs[grp[k]].index;
+                run_typed_group(cl, imgs, tv.data(), grp, crops != nullptr, *cfg, stream, &r);
+                r.scatter(idx, out, status);
+            }
+        });
+    return count_failures(status, n_images);
+}
+
+extern "C" int phd_decode_views_device(const phd_typed_view* views, int n_images, double* const* d_planes,
+                                       void* stream) {
+    clear_error();
+    if (!views || !d_planes || n_images <= 0) {
+        set_error("phd_decode_views_device: bad arguments");
+        return -1;
+    }
+    for (int i = 0; i < n_images; i++) {
+        std::string why;
+        if (!d_planes[i]) why = "destination is NULL";
+        if (!why.empty() || !typed_view_why(views[i], &why)) {
+            set_error("image " + std::to_string(i) + ": " + why);
+            return -1;
+        }
+    }
+    Context* c = get_context();
+    if (!c) return -1;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const hipStream_t st = work_stream(c, stream);
+    for (int i = 0; i < n_images; i++)
+        if (!enqueue_decode_view(c, views[i], d_planes[i], st)) return -1;
+    if (!stream) {
+        const hipError_t e = hipStreamSynchronize(st);
+        if (e != hipSuccess) {
+            set_error(std::string("phd_decode_views_device: ") + hipGetErrorString(e));
+            return -1;
+        }
+        c->prof.collect();
+    }
+    return 0;
+}
+
 extern "C" int phd_report_batch_u8_crops(const uint8_t* const* images, const int* heights, const int* widths,
                                          int n_images, const phd_config* cfg, const Crop_Boundaries* const* crops,
                                          Full_Report_Data** out, int* status) {

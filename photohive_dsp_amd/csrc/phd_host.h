@@ -131,8 +131,10 @@ bool gfft_run(const GfftPlan& p, const double2* in, double2* out, long count, do
 
 // ---- per-kernel event timing (opt-in, phd_profile_kernels) -----------------
 enum KernelId {
-    kK1 = 0, kFftRows = 1, kFftCols = 2, kCutoffs = 3, kPalSums = 4, kSharp = 5, kPack = 6, kNumKernels = 7
+    kK1 = 0, kFftRows = 1, kFftCols = 2, kCutoffs = 3, kPalSums = 4, kSharp = 5, kPack = 6, kClassify = 7,
+    kDecode = 8, kNumKernels = 9
 };
+static_assert(kClassify == kProfClassify && kDecode == kProfDecode, "the decode launches' profiler slots");
 struct KernelProfiler {
     unsigned mask = 0;                              // kernels to bracket with events
     // mask bits 24-30: stride s > 1, only every s-th batch call is bracketed
@@ -237,6 +239,9 @@ struct Context {
     void* h_views = nullptr;
     size_t h_views_bytes = 0;
     hipEvent_t ev_views = nullptr;
+    // typed views: the snap tables' device copy (views_plan.h: snap_tables); the
+    // classifier's table and flag words share d_views / h_views with the pack launch
+    uint8_t* d_snap = nullptr;
     hipEvent_t ev[8] = {};
     // two streams per context: `stream` (K1, then the FFT chain) and `tail`
     // (the A-record download, the palette's second pass -- rules upload, Kcut,
@@ -398,6 +403,12 @@ bool legacy_release(Full_Report_Data* r);
 // RGB8 pipeline when every value is k/255.0, else the fp64 planar kernels.
 Full_Report_Data* report_planar(Context* c, const double* r, const double* g, const double* b, int height,
                                 int width, const phd_config& cfg, const Crop_Boundaries* crops);
+// report_planar after its upload: the fp64 planar pipeline on planes already
+// in c->d_planes (4 n doubles: P.r | P.g | P.b | luma) on the idle stream st;
+// cfg, the size and the boxes validated by the caller.  The typed entry runs
+// it on the planes k_decode_view filled.
+Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int height, int width, const phd_config& cfg,
+                                       const Crop_Boundaries* crops, hipStream_t st);
 // Run the full report on n same-size device images.  out[i]/status[i] per image.
 // crops: one set of boxes for every image (the single-image entries; two
 // launches per box, sharpness.hip's k_sharp_pass).  img_crops (crops must be
@@ -417,6 +428,14 @@ bool enqueue_sharpness(Context* c, const uint8_t* const* d_imgs, int n, int widt
 // one read in place).  The table goes up through the context's pinned copy;
 // the launch is followed by c->ev_views.  views: validated (view_why).
 bool enqueue_pack_views(Context* c, const phd_image_view* views, uint8_t* const* dst, int n, hipStream_t st);
+// The classify launch of a group's typed views on st (decode_views.hip): view
+// i's packed RGB8 image goes to dst[i] (3 * height * width bytes), its flag
+// word (kDecNotU8 | kDecNonFinite, decode_view.h) to flags[i] on the host.  The
+// table and the flag words go through d_views / h_views as the pack launch's
+// do; returns with the flags read back (st drained).  views: validated.
+bool classify_views(Context* c, const phd_typed_view* views, uint8_t* const* dst, int n, hipStream_t st, int* flags);
+// The decode launch of one validated view into planes (3 * height * width doubles) on st.
+bool enqueue_decode_view(Context* c, const phd_typed_view& view, double* planes, hipStream_t st);
 // Palette intermediates only (for parity tests).
 bool run_palette_trace(Context* c, const uint8_t* d_img, int height, int width, const phd_config& cfg,
                        std::vector<unsigned>* hist, PaletteDecision* dec,

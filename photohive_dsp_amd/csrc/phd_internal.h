@@ -417,6 +417,17 @@ int prof_begin_pack(KernelProfiler* prof, hipStream_t st);
 hipError_t launch_pack_views(const PackRec* d_recs, int n, int max_bands, hipStream_t st,
                              KernelProfiler* prof = nullptr);
 
+// ---- typed image views (decode_views.hip, decode_view.h) ----------------------
+// The classifier of n typed views (d_recs: the device table; d_flags[n], zeroed)
+// in one launch over (row band, view), and the decode of one view into its
+// record's planes.  kernel: a KernelId (phd_host.h).
+struct DecodeRec;
+constexpr int kProfClassify = 7, kProfDecode = 8;
+int prof_begin_kernel(KernelProfiler* prof, int kernel, hipStream_t st);
+hipError_t launch_classify_views(const DecodeRec* d_recs, int* d_flags, int n, int max_bands, hipStream_t st,
+                                 KernelProfiler* prof = nullptr);
+hipError_t launch_decode_view(const DecodeRec& rec, hipStream_t st, KernelProfiler* prof = nullptr);
+
 // ---- fp64 planar input of the legacy entry point (planar.hip) ---------------
 struct PlanarSrc {
     const double* r;

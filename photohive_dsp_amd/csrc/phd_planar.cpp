@@ -13,6 +13,10 @@
 // rejected with NULL, like its other undefined cases.  Any other finite values
 // (negative channels, luma outside [0, 1]) get a report: the polar bins'
 // fixed-point scale follows the image's largest |pgm - avg| (bin_scale).
+//
+// report_planar is the upload and the 8-bit test; report_planes_device is the
+// fp64 pipeline on planes that are on the device, which the typed views' entry
+// (phd_entries.cpp) also runs on the planes k_decode_view filled.
 #include <cmath>
 #include <cstring>
 
@@ -81,14 +85,6 @@ Full_Report_Data* report_planar(Context* c, const double* r, const double* g, co
         return nullptr;
     double* dp = c->d_planes;
     const PlanarSrc P{dp, dp + n, dp + 2 * n};
-    double* pgm = dp + 3 * n;
-    const int nb = planar_blocks(n);
-    const GridParams gp = make_grid(cfg);
-    const int ds = cfg.downsample_rate > 1 ? cfg.downsample_rate : 1;
-    const long n_hsv = hsv_count(height, width, ds);
-    const int nchunks = (int)((n_hsv + kChunk - 1) / kChunk);
-    const int nbins = cfg.radius_partitions * cfg.angle_partitions, wf = width / 2 + 1;
-    const int ncrops = crops ? crops->N : 0;
     if (!ensure_device(&c->d_prec, &c->prec_bytes, kAlign)) return nullptr;
     int* flags = (int*)c->d_prec;
     PHD_HIPN(hipMemsetAsync(flags, 0, sizeof(int), st));
@@ -108,6 +104,26 @@ Full_Report_Data* report_planar(Context* c, const double* r, const double* g, co
         (void)hipStreamSynchronize(c->stream);
         return out;
     }
+    return report_planes_device(c, P, height, width, cfg, crops, st);
+}
+
+// Everything after the upload: the fp64 planar pipeline on planes that are on
+// the device already -- P.r | P.g | P.b are the first 3 n doubles of
+// c->d_planes (4 n doubles), whose fourth plane takes the luma.  cfg, the size
+// and the boxes are validated; nothing but the planes' own producer is queued
+// on st (no buffer allocated here is in use).
+Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int height, int width, const phd_config& cfg,
+                                       const Crop_Boundaries* crops, hipStream_t st) {
+    std::string why;
+    const long n = (long)height * width;
+    double* pgm = c->d_planes + 3 * n;
+    const int nb = planar_blocks(n);
+    const GridParams gp = make_grid(cfg);
+    const int ds = cfg.downsample_rate > 1 ? cfg.downsample_rate : 1;
+    const long n_hsv = hsv_count(height, width, ds);
+    const int nchunks = (int)((n_hsv + kChunk - 1) / kChunk);
+    const int nbins = cfg.radius_partitions * cfg.angle_partitions, wf = width / 2 + 1;
+    const int ncrops = crops ? crops->N : 0;
     // every allocation of the planar pipeline before its first launch (the stream is idle)
     FftSel fs;
     if (!select_generic(c, height, width, nbins, &fs)) return nullptr;
@@ -119,7 +135,7 @@ Full_Report_Data* report_planar(Context* c, const double* r, const double* g, co
         !ensure_device((void**)&c->d_inter, &c->inter_bytes, sizeof(double2) * ((size_t)height * wf + 1024)))
         return nullptr;
     uint8_t* dr = (uint8_t*)c->d_prec;
-    flags = (int*)(dr + R.flags);
+    int* flags = (int*)(dr + R.flags);
     PHD_HIPN(hipMemsetAsync(dr, 0, R.total, st));
     // ---- the fp64 planar pipeline -------------------------------------------------
     double* avg = (double*)(dr + R.avg);

@@ -160,6 +160,54 @@ bool enqueue_pack_views(Context* c, const phd_image_view* views, uint8_t* const*
     return true;
 }
 
+// the snap tables' device copy (uploaded once per context)
+static const uint8_t* device_snap(Context* c) {
+    if (c->d_snap) return c->d_snap;
+    uint8_t* d = nullptr;
+    if (hipMalloc((void**)&d, kSnapBytes) != hipSuccess ||
+        hipMemcpy(d, snap_tables(), kSnapBytes, hipMemcpyHostToDevice) != hipSuccess) {
+        if (d) (void)hipFree(d);
+        set_error("snap table upload failed");
+        return nullptr;
+    }
+    return c->d_snap = d;
+}
+
+bool classify_views(Context* c, const phd_typed_view* views, uint8_t* const* dst, int n, hipStream_t st, int* flags) {
+    if (n <= 0) return true;
+    const uint8_t* snap = device_snap(c);
+    if (!snap) return false;
+    std::vector<DecodeRec> recs(n);
+    int max_bands = 0;
+    for (int i = 0; i < n; i++) {
+        recs[i] = decode_record(views[i], nullptr, dst[i], snap);
+        max_bands = std::max(max_bands, (recs[i].height + recs[i].band_rows - 1) / recs[i].band_rows);
+    }
+    // the table of the last pack or classify launch is still read until that launch is done
+    if (!c->ev_views) PHD_HIP(hipEventCreateWithFlags(&c->ev_views, hipEventDisableTiming));
+    else PHD_HIP(hipEventSynchronize(c->ev_views));
+    // records | flag words (zero), one upload
+    const size_t o_flags = al(sizeof(DecodeRec) * (size_t)n), bytes = o_flags + sizeof(int) * (size_t)n;
+    if (!ensure_device(&c->d_views, &c->views_bytes, bytes)) return false;
+    if (!grow_pinned(&c->h_views, &c->h_views_bytes, bytes)) return false;
+    uint8_t* hv = (uint8_t*)c->h_views;
+    uint8_t* dv = (uint8_t*)c->d_views;
+    memset(hv, 0, bytes);
+    memcpy(hv, recs.data(), sizeof(DecodeRec) * (size_t)n);
+    PHD_HIP(hipMemcpyAsync(dv, hv, bytes, hipMemcpyHostToDevice, st));
+    PHD_HIP(launch_classify_views((const DecodeRec*)dv, (int*)(dv + o_flags), n, max_bands, st, &c->prof));
+    PHD_HIP(hipMemcpyAsync(hv + o_flags, dv + o_flags, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
+    PHD_HIP(hipEventRecord(c->ev_views, st));
+    PHD_HIP(hipStreamSynchronize(st));
+    memcpy(flags, hv + o_flags, sizeof(int) * (size_t)n);
+    return true;
+}
+
+bool enqueue_decode_view(Context* c, const phd_typed_view& view, double* planes, hipStream_t st) {
+    PHD_HIP(launch_decode_view(decode_record(view, planes, nullptr, nullptr), st, &c->prof));
+    return true;
+}
+
 // pre_compute_error_checks (src/utilities.c:64-87) on the dimensions.
 bool precheck(int height, int width) {
     if (height < 350 || width < 350) {

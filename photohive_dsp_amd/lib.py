@@ -4,7 +4,7 @@ import ctypes
 import os
 
 from .structures import (Blur_Profile, Blur_Vector, Crop_Boundaries, Full_Report_Data, Image_PGM, Image_RGB,
-                         PhdConfig, PhdImageView, RGB_Statistics)
+                         PhdConfig, PhdImageView, PhdTypedView, RGB_Statistics)
 
 def _preload_torch_hip_runtime():
     """One HIP runtime per process.  PyTorch-ROCm ships its own libamdhip64.so
@@ -111,6 +111,8 @@ lib.phd_set_lanes.restype = ctypes.c_int
 lib.phd_set_lanes.argtypes = [ctypes.c_int]
 KERNELS = ["hsv_stats", "fft_rows", "fft_cols", "palette_cutoffs", "palette_sums", "sharpness"]
 PACK_VIEWS_KERNEL = 6      # the image views' gather (bit 6 of phd_profile_kernels: "pack_views")
+CLASSIFY_VIEWS_KERNEL = 7  # the typed views' classifier (bit 7: "classify_views")
+DECODE_VIEWS_KERNEL = 8    # the typed views' decode to double planes (bit 8: "decode_views")
 lib.phd_debug_time_kernel.restype = ctypes.c_int
 lib.phd_debug_time_kernel.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, P(PhdConfig),
                                       ctypes.c_int, ctypes.c_int, P(ctypes.c_double)]
@@ -161,7 +163,15 @@ for _name, _res, _args in (("phd_shutdown", None, []),
                              P(P(Full_Report_Data)), P(ctypes.c_int), ctypes.c_void_p]),
                            ("phd_pack_views_device", ctypes.c_int,
                             [P(PhdImageView), ctypes.c_int, P(ctypes.c_void_p), ctypes.c_void_p]),
-                           ("phd_debug_pack_view_host", ctypes.c_int, [P(PhdImageView), ctypes.c_void_p])):
+                           ("phd_debug_pack_view_host", ctypes.c_int, [P(PhdImageView), ctypes.c_void_p]),
+                           # device images of any element type (views: n PhdTypedView)
+                           ("phd_report_batch_device_typed_views", ctypes.c_int,
+                            [P(PhdTypedView), ctypes.c_int, P(PhdConfig), P(P(Crop_Boundaries)),
+                             P(P(Full_Report_Data)), P(ctypes.c_int), ctypes.c_void_p]),
+                           ("phd_decode_views_device", ctypes.c_int,
+                            [P(PhdTypedView), ctypes.c_int, P(ctypes.c_void_p), ctypes.c_void_p]),
+                           ("phd_debug_decode_view_host", ctypes.c_int,
+                            [P(PhdTypedView), ctypes.c_void_p, ctypes.c_void_p, P(ctypes.c_int)])):
     try:
         _f = getattr(lib, _name)
     except AttributeError:

@@ -79,3 +79,18 @@ class PhdImageView(Structure):
     data + y*row_stride + x*pixel_stride + c*channel_stride."""
     _fields_ = [("data", c_void_p), ("height", c_int), ("width", c_int),
                 ("row_stride", c_int64), ("pixel_stride", c_int64), ("channel_stride", c_int64)]
+
+
+class PhdTypedView(Structure):
+    """One device-resident image of 8- / 16-bit integers, halves, floats or doubles as a
+    byte-strided view (include/photohive_dsp.h: phd_typed_view): channel c of pixel (y, x)
+    is the element at data + y*row_stride + x*pixel_stride + c*channel_stride (bytes) and
+    its value is (double)element / max_value (0: the type's own 255, 65535 or 1.0)."""
+    _fields_ = [("data", c_void_p), ("height", c_int), ("width", c_int),
+                ("row_stride", c_int64), ("pixel_stride", c_int64), ("channel_stride", c_int64),
+                ("elem", c_int), ("flags", c_int), ("max_value", c_double)]
+
+
+# phd_typed_view.elem and .flags
+PHD_ELEM_U8, PHD_ELEM_U16, PHD_ELEM_F16, PHD_ELEM_F32, PHD_ELEM_F64 = range(5)
+PHD_VIEW_SNAP_U8 = 1
