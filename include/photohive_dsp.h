@@ -363,6 +363,91 @@ int phd_decode_views_device(const phd_typed_view* views, int n_images, double* c
  * NULL).  0, or -1 with phd_last_error. */
 int phd_debug_decode_view_host(const phd_typed_view* view, double* planes, uint8_t* rgb8, int* is_u8);
 
+/* ---- device YCbCr frames ---------------------------------------------------------
+ * The reference reports on RGB planes (Image_RGB, src/image_processing.h:31-36);
+ * the JPEG and video decoders that feed a GPU pipeline emit 8-bit YCbCr: NV12
+ * surfaces with a pitch, planar 4:2:0, 4:2:2 or 4:4:4, packed YUY2.  A YUV view
+ * describes such a frame and the library converts it, in one launch per run
+ * for all its views, into a packed RGB8 image of its own; the report is the
+ * report of that image, field for field.  The conversion is defined in
+ * integers, so every caller gets the same RGB8 bytes for the same frame.
+ *
+ * Step 1, chroma at pixel (y, x) of a plane c (cb or cr) of ch x cw samples,
+ * sx = chroma_shift_x, sy = chroma_shift_y, indices clamped to the plane:
+ *   REPLICATE:        C = c[y >> sy][x >> sx]
+ *   TRIANGLE, 4:4:4:  C = c[y][x]
+ *   TRIANGLE, 4:2:2:  i = x >> 1, far = i-1 (x even) or i+1 (x odd), clamped to
+ *                     [0, cw-1];  C = (3*c[y][i] + c[y][far] + (x odd ? 2 : 1)) >> 2
+ *   TRIANGLE, 4:2:0:  j = y >> 1, farrow = j-1 (y even) or j+1 (y odd), clamped to
+ *                     [0, ch-1];  t[k] = 3*c[j][k] + c[farrow][k];
+ *                     C = (3*t[i] + t[far] + (x odd ? 7 : 8)) >> 4
+ * (the weights and rounding of libjpeg's "fancy" upsampling).
+ * Step 2, the matrix, in int32 with arithmetic shifts: u = Cb - 128,
+ * v = Cr - 128, yy = cy*(Y - yoff),
+ *   R = clamp8((yy + crv*v + 32768) >> 16)
+ *   G = clamp8((yy - cgu*u - cgv*v + 32768) >> 16)
+ *   B = clamp8((yy + cbu*u + 32768) >> 16)
+ *   matrix, range        cy     crv     cgu    cgv    cbu     yoff
+ *   BT601 FULL (JFIF)    65536  91881   22554  46802  116130  0
+ *   BT601 LIMITED        76309  104597  25675  53279  132201  16
+ *   BT709 FULL           65536  103206  12276  30679  121609  0
+ *   BT709 LIMITED        76309  117489  13975  34925  138438  16
+ * The JFIF row holds libjpeg's constants (cgu 22554); the others are
+ * round(value * 65536).  Every row stays within 0.504 of the clamped
+ * real-valued result (0.5 + 511 * 0.5 / 65536). */
+enum { PHD_YUV_BT601 = 0, PHD_YUV_BT709 = 1 };
+enum { PHD_YUV_FULL = 0, PHD_YUV_LIMITED = 1 };
+enum { PHD_YUV_CHROMA_REPLICATE = 0, PHD_YUV_CHROMA_TRIANGLE = 1 };
+
+/* One device-resident 8-bit YCbCr frame.  Luma of pixel (y, x) is the byte at
+ *   y + y*y_row_stride + x*y_pixel_stride,
+ * chroma sample (j, i) the byte at cb + j*c_row_stride + i*c_pixel_stride and
+ * the same from cr; the chroma planes are ch = (height + sy) >> sy rows of
+ * cw = (width + sx) >> sx samples.  I420 / YV12: three planes; NV12:
+ * c_pixel_stride 2, cr = cb + 1; NV21: cb = cr + 1; I422, I444: three planes,
+ * shifts (1,0) and (0,0); YUY2: y_pixel_stride 2, c_pixel_stride 4,
+ * cb = y + 1, cr = y + 3, shifts (1,0); UYVY: the same with the pointers moved;
+ * pitched surfaces: a row stride larger than the row; a region of a larger
+ * frame: pointers at the region's first sample, even origin.  (4:0:0 is an
+ * expanded grey plane phd_image_view.)
+ * Valid: the three pointers non-NULL, height and width > 0, the shifts one of
+ * the three pairs, every enum in range, y_pixel_stride != 0 when width > 1,
+ * y_row_stride != 0 when height > 1, c_pixel_stride != 0 when cw > 1,
+ * c_row_stride != 0 when ch > 1. */
+typedef struct phd_yuv_view {
+    const uint8_t *y, *cb, *cr;            /* sample (0,0) of each plane */
+    int height, width;                     /* luma size */
+    int64_t y_row_stride, y_pixel_stride;  /* BYTES; may be negative */
+    int64_t c_row_stride, c_pixel_stride;  /* BYTES; shared by cb and cr */
+    int chroma_shift_x, chroma_shift_y;    /* (0,0) 4:4:4, (1,0) 4:2:2, (1,1) 4:2:0 */
+    int matrix, range, chroma;             /* PHD_YUV_* */
+} phd_yuv_view;
+
+/* phd_report_batch_device_views over YUV views (get_full_report_data,
+ * src/interface.c:20-94, per image, on the Image_RGB, src/image_processing.h:
+ * 31-36, the conversion above defines): the same semantics, return values and
+ * per-image failure rules; any sizes, size groups on the lanes, boxes in luma
+ * coordinates, the reference's size checks (src/utilities.c:64-87) before
+ * anything is read.  A bad view fails alone and phd_last_error names the image
+ * and the field.  No byte outside the union of the three planes' spans is
+ * read. */
+int phd_report_batch_device_yuv(const phd_yuv_view* views, int n_images, const phd_config* cfg,
+                                const Crop_Boundaries* const* crops, Full_Report_Data** out, int* status,
+                                void* stream);
+
+/* The conversion alone (the Image_RGB of src/image_processing.h:31-36 as
+ * packed bytes, the input of get_full_report_data, src/interface.c:20-94):
+ * d_dst[i] (device) receives the 3*height*width RGB8 bytes of view i; any size
+ * from 1x1.  Enqueued on `stream`, or (NULL) on the library's stream and waited
+ * for.  A bad view fails the call.  0 or -1. */
+int phd_convert_yuv_device(const phd_yuv_view* views, int n_images, uint8_t* const* d_dst, void* stream);
+
+/* Validation hook, host only (no GPU): the conversion kernel's row code
+ * (yuv_view.h; the reference reads its Image_RGB planes per pixel,
+ * src/image_processing.h:31-36, src/interface.c:20-94) over one view of host
+ * memory into dst[3*height*width].  0, or -1 with phd_last_error. */
+int phd_debug_yuv_view_host(const phd_yuv_view* view, uint8_t* dst);
+
 /* Palette intermediates of one device-resident image, for bit-exact checks:
  * hist[TL] (arm_octree quantities), parents[*n_parents] (valid_parents in
  * palette order), kept[*n_parents] (pixels surviving group_irregular_pixels).
@@ -461,7 +546,7 @@ int phd_last_timings(double* ms, int n);
 /* Per-kernel GPU time from HIP events recorded on the launch stream around
  * every launch of the kernels in `mask` (bit k = kernel k: 0 hsv_stats,
  * 1 fft_rows, 2 fft_cols, 3 palette_cutoffs, 4 palette_sums, 5 sharpness,
- * 6 pack_views, 7 classify_views, 8 decode_views).
+ * 6 pack_views, 7 classify_views, 8 decode_views, 9 yuv_views).
  * phd_profile_kernels resets the counters; phd_profile_read returns the
  * accumulated milliseconds and launch count of one kernel. */
 int phd_profile_kernels(unsigned mask);

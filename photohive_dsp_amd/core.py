@@ -19,8 +19,9 @@ import numpy as np
 
 from .lib import last_error, lib
 from .structures import (PHD_ELEM_F16, PHD_ELEM_F32, PHD_ELEM_F64, PHD_ELEM_U8, PHD_ELEM_U16, PHD_VIEW_SNAP_U8,
-                         Crop_Boundaries, Full_Report_Data, PhdConfig, PhdImageView, PhdTypedView, Pixel_HSV,
-                         RGB_Statistics)
+                         PHD_YUV_BT601, PHD_YUV_BT709, PHD_YUV_CHROMA_REPLICATE, PHD_YUV_CHROMA_TRIANGLE,
+                         PHD_YUV_FULL, PHD_YUV_LIMITED, Crop_Boundaries, Full_Report_Data, PhdConfig, PhdImageView,
+                         PhdTypedView, PhdYuvView, Pixel_HSV, RGB_Statistics)
 from .utils import hsv_to_rgb, image_pgm_to_pillow, to_rgb8
 
 DEFAULTS = dict(h_partitions=18, s_partitions=2, v_partitions=3, black_thresh=0.1, gray_thresh=0.1,
@@ -472,6 +473,134 @@ def decode_views_device(images, layout="HWC", bgr=False, max_value=None, stream=
     dst = (ctypes.c_void_p * n)(*[o.data_ptr() for o in out])
     if lib.phd_decode_views_device(views, n, dst, _stream_handle(stream)) != 0:
         raise RuntimeError(f"decode_views_device failed: {last_error()}")
+    return out
+
+
+def nv12_planes(surface, height, width):
+    """The (y, uv) planes of an NV12 decoder surface, with no copy: `surface`
+    is a 2-D uint8 tensor [>= height + ch, pitch] (pitch >= width rounded up to
+    even) holding height luma rows and then ch = (height + 1) // 2 rows of
+    interleaved Cb Cr pairs.  Returns y [height, width] and uv [ch, cw, 2]
+    views of it (cw = (width + 1) // 2), make_yuv_views' (y, uv) frame."""
+    ch, cw = (height + 1) // 2, (width + 1) // 2
+    if surface.dim() != 2 or surface.shape[0] < height + ch or surface.shape[1] < max(width, 2 * cw):
+        raise ValueError(f"expected a 2-D surface of at least {height + ch} rows of {max(width, 2 * cw)} bytes, "
+                         f"got {tuple(surface.shape)}")
+    y = surface[:height, :width]
+    uv = surface[height:height + ch, :2 * cw].unflatten(1, (cw, 2))
+    return y, uv
+
+
+_YUV_MATRICES = {"bt601": PHD_YUV_BT601, "bt709": PHD_YUV_BT709}
+_YUV_CHROMA = {"replicate": PHD_YUV_CHROMA_REPLICATE, "triangle": PHD_YUV_CHROMA_TRIANGLE}
+
+
+def make_yuv_views(frames, matrix="bt601", full_range=True, chroma="replicate", swap_uv=False):
+    """The PhdYuvView descriptors of 8-bit YCbCr frames held in uint8 torch
+    tensors, with no copy.  Each frame is (y, cb, cr), three 2-D tensors (I420,
+    I422, I444 and their pitched or cropped views); (y, uv) with uv of shape
+    [ch, cw, 2], interleaved Cb Cr (NV12; nv12_planes splits a decoder
+    surface); or a PhdYuvView, taken as it is (YUY2, memory that is no
+    tensor).  swap_uv=True reads the chroma as Cr Cb (NV21; YV12 for three
+    planes).  The subsampling is inferred from the shapes: chroma of
+    (H, W) is 4:4:4, (H, (W + 1) // 2) 4:2:2, ((H + 1) // 2, (W + 1) // 2)
+    4:2:0.  matrix: "bt601" or "bt709"; full_range: JFIF's 0..255, else
+    16..235 / 16..240; chroma: "replicate" or "triangle" (libjpeg's fancy
+    upsampling).  Pure stride arithmetic on data_ptr() and stride(): needs no
+    GPU (CPU tensors work).  Returns (array of PhdYuvView, objects to keep
+    alive while the views are in use)."""
+    import torch
+    if matrix not in _YUV_MATRICES:
+        raise ValueError(f"matrix must be 'bt601' or 'bt709', not {matrix!r}")
+    if chroma not in _YUV_CHROMA:
+        raise ValueError(f"chroma must be 'replicate' or 'triangle', not {chroma!r}")
+    frames = list(frames)
+    views = (PhdYuvView * max(1, len(frames)))()
+
+    def plane(i, t, dims, what):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != dims:
+            raise ValueError(f"image {i}: {what} must be a {dims}-D uint8 torch tensor")
+        return t
+
+    for i, f in enumerate(frames):
+        if isinstance(f, PhdYuvView):
+            views[i] = f
+            continue
+        if not isinstance(f, (tuple, list)) or len(f) not in (2, 3):
+            raise ValueError(f"image {i}: expected (y, cb, cr), (y, uv) or a PhdYuvView")
+        y = plane(i, f[0], 2, "y")
+        h, w = int(y.shape[0]), int(y.shape[1])
+        if h < 1 or w < 1:
+            raise ValueError(f"image {i}: empty luma plane {tuple(y.shape)}")
+        if len(f) == 2:
+            uv = plane(i, f[1], 3, "uv")
+            if uv.shape[2] != 2:
+                raise ValueError(f"image {i}: uv must have shape [ch, cw, 2], got {tuple(uv.shape)}")
+            cshape, (crs, cps, pair) = tuple(uv.shape[:2]), uv.stride()
+            cb, cr = uv.data_ptr(), uv.data_ptr() + pair
+        else:
+            pb, pr = plane(i, f[1], 2, "cb"), plane(i, f[2], 2, "cr")
+            if pb.shape != pr.shape or pb.stride() != pr.stride():
+                raise ValueError(f"image {i}: cb and cr differ in shape or strides "
+                                 f"({tuple(pb.shape)} {pb.stride()} and {tuple(pr.shape)} {pr.stride()})")
+            cshape, (crs, cps) = tuple(pb.shape), pb.stride()
+            cb, cr = pb.data_ptr(), pr.data_ptr()
+        # (a single row or column fits several: the least subsampled reading)
+        fits = [s for s in ((0, 0), (1, 0), (1, 1)) if cshape == ((h + s[1]) >> s[1], (w + s[0]) >> s[0])]
+        if not fits:
+            raise ValueError(f"image {i}: chroma of shape {cshape} fits no subsampling of a {h} x {w} luma plane")
+        sx, sy = fits[0]
+        if swap_uv:
+            cb, cr = cr, cb
+        yrs, yps = y.stride()
+        views[i] = PhdYuvView(y.data_ptr(), cb, cr, h, w, int(yrs), int(yps), int(crs), int(cps), sx, sy,
+                              _YUV_MATRICES[matrix], PHD_YUV_FULL if full_range else PHD_YUV_LIMITED,
+                              _YUV_CHROMA[chroma])
+    return views, frames
+
+
+def reports_device_yuv(frames, matrix="bt601", full_range=True, chroma="replicate", swap_uv=False, stream=None,
+                       salient_characters=None, **kw):
+    """Reports for 8-bit YCbCr frames on the current GPU (make_yuv_views: NV12
+    surfaces, planar 4:2:0 / 4:2:2 / 4:4:4, YUY2 descriptors; any sizes): each
+    frame is converted to RGB8 by the library's integer conversion
+    (include/photohive_dsp.h), one launch per run, and reported as that image
+    (phd_report_batch_device_yuv).  salient_characters: per-image crop boxes
+    in luma coordinates (normalize_salient)."""
+    views, keep = make_yuv_views(frames, matrix, full_range, chroma, swap_uv)
+    n = len(keep)
+    cfg = make_config(**kw)
+    crops = normalize_salient(salient_characters, n)
+    outs = (POINTER(Full_Report_Data) * n)()
+    st = (ctypes.c_int * n)()
+    s = _stream_handle(stream)
+    lib.phd_report_batch_device_yuv(views, n, ctypes.byref(cfg), crops[0] if crops else None, outs, st, s)
+    res = [(_finish(outs[i], views[i].height, views[i].width, kw) if st[i] == 0 else None) for i in range(n)]
+    if any(r is None for r in res):
+        err = last_error()
+        del res                     # (the reports that did come back are freed)
+        raise RuntimeError(f"reports_device_yuv failed: {err}")
+    return res
+
+
+def convert_yuv_device(frames, matrix="bt601", full_range=True, chroma="replicate", swap_uv=False, stream=None):
+    """The conversion alone (phd_convert_yuv_device): packed [H, W, 3] uint8
+    device tensors of the given frames (make_yuv_views), for the stage-only
+    calls and for callers that want the library's RGB8 bytes."""
+    import torch
+    views, keep = make_yuv_views(frames, matrix, full_range, chroma, swap_uv)
+    n = len(keep)
+    if n == 0:
+        return []
+
+    def device(f):
+        return f[0].device if isinstance(f, (tuple, list)) else "cuda"
+
+    out = [torch.empty((views[i].height, views[i].width, 3), dtype=torch.uint8, device=device(keep[i]))
+           for i in range(n)]
+    dst = (ctypes.c_void_p * n)(*[o.data_ptr() for o in out])
+    if lib.phd_convert_yuv_device(views, n, dst, _stream_handle(stream)) != 0:
+        raise RuntimeError(f"convert_yuv_device failed: {last_error()}")
     return out
 
 

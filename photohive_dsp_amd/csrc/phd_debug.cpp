@@ -328,3 +328,12 @@ extern "C" int phd_debug_decode_view_host(const phd_typed_view* view, double* pl
     if (rc != 0) set_error(why);
     return rc;
 }
+
+// The YUV conversion kernel's host twin (phd_yuv.cpp: yuv_view_host) behind the C ABI.
+extern "C" int phd_debug_yuv_view_host(const phd_yuv_view* view, uint8_t* dst) {
+    clear_error();
+    std::string why;
+    const int rc = yuv_view_host(view, dst, &why);
+    if (rc != 0) set_error(why);
+    return rc;
+}

@@ -491,6 +491,7 @@ struct BatchImage {
     const phd_image_view* view;      // its view, gathered on the lane unless packed already
     int height, width;
     const Crop_Boundaries* boxes;    // NULL: none
+    const phd_yuv_view* yuv = nullptr;   // a YCbCr frame, converted on the lane (ptr and view NULL)
 };
 
 // One group of a batch large enough for two lanes (two-lane calls on the
@@ -532,6 +533,25 @@ static bool stage_views(Context* cl, const std::vector<BatchImage>& imgs, const 
     return precheck(height, width) && enqueue_pack_views(cl, gv.data(), dst.data(), gm, work_stream(cl, stream));
 }
 
+// The image pointers of a group of YUV views: every view's staging image on
+// the lane (256-byte steps), converted by one launch on the call's stream.
+static bool stage_yuv(Context* cl, const std::vector<BatchImage>& imgs, const std::vector<int>& grp, void* stream,
+                      const uint8_t** ptrs) {
+    const int gm = (int)grp.size(), height = imgs[grp[0]].height, width = imgs[grp[0]].width;
+    // (the reference's size checks come first: a size it rejects is not read)
+    if (!precheck(height, width)) return false;
+    const size_t step = (3 * (size_t)height * width + 255) & ~(size_t)255;
+    if (!ensure_device((void**)&cl->d_vstage, &cl->vstage_bytes, (size_t)gm * step)) return false;
+    std::vector<phd_yuv_view> gv(gm);
+    std::vector<uint8_t*> dst(gm);
+    for (int k = 0; k < gm; k++) {
+        gv[k] = *imgs[grp[k]].yuv;
+        dst[k] = cl->d_vstage + (size_t)k * step;
+        ptrs[k] = dst[k];
+    }
+    return enqueue_yuv_views(cl, gv.data(), dst.data(), gm, work_stream(cl, stream));
+}
+
 // Runs the groups (indices into imgs, one same-size run_reports call each) on
 // the lanes and returns the call's failure count.  Two lanes when there are
 // two or more groups on the library's streams: lane L starts with group L,
@@ -552,7 +572,9 @@ static int run_device_batch(Context* c, const std::vector<BatchImage>& imgs,
             idx[k] = imgs[grp[k]].index;
         }
         RunResults r(gm);
-        if (imgs[grp[0]].view == nullptr || stage_views(cl, imgs, grp, stream, ptrs.data()))
+        const BatchImage& first = imgs[grp[0]];
+        if (first.yuv ? stage_yuv(cl, imgs, grp, stream, ptrs.data())
+                      : first.view == nullptr || stage_views(cl, imgs, grp, stream, ptrs.data()))
             run_reports(cl, ptrs.data(), gm, imgs[grp[0]].height, imgs[grp[0]].width, cfg, nullptr, r.o.data(),
                         r.st.data(), (hipStream_t)stream, boxes ? cr.data() : nullptr);
         r.scatter(idx, out, status);
@@ -704,6 +726,67 @@ extern "C" int phd_pack_views_device(const phd_image_view* views, int n_images, 
         const hipError_t e = hipStreamSynchronize(st);
         if (e != hipSuccess) {
             set_error(std::string("phd_pack_views_device: ") + hipGetErrorString(e));
+            return -1;
+        }
+        c->prof.collect();
+    }
+    return 0;
+}
+
+// Device YCbCr frames (the input of get_full_report_data, src/interface.c:20-94,
+// as decoders emit it: yuv_view.h): the views call over YUV views, each
+// converted into its lane's staging image.
+extern "C" int phd_report_batch_device_yuv(const phd_yuv_view* views, int n_images, const phd_config* cfg,
+                                           const Crop_Boundaries* const* crops, Full_Report_Data** out, int* status,
+                                           void* stream) {
+    clear_error();
+    if (!views || !cfg || !out || !status || n_images <= 0) {
+        set_error("phd_report_batch_device_yuv: bad arguments");
+        return -1;
+    }
+    // a bad view or bad boxes fail their image alone (the last message stays)
+    std::vector<BatchImage> imgs;
+    std::string bad;
+    for (int i = 0; i < n_images; i++) {
+        out[i] = nullptr;
+        status[i] = -1;
+        std::string why;
+        if (yuv_view_why(views[i], &why) && (!crops || crops_why(crops[i], views[i].height, views[i].width, &why)))
+            imgs.push_back({i, nullptr, nullptr, views[i].height, views[i].width, crops ? crops[i] : nullptr,
+                            &views[i]});
+        else bad = "image " + std::to_string(i) + ": " + why;
+    }
+    Context* c = get_context();
+    if (!c) return -1;
+    if (!bad.empty()) set_error(bad);
+    auto groups = mixed_groups(imgs);
+    split_for_lanes(&groups, stream);
+    return run_device_batch(c, imgs, groups, crops != nullptr, *cfg, out, status, n_images, stream);
+}
+
+extern "C" int phd_convert_yuv_device(const phd_yuv_view* views, int n_images, uint8_t* const* d_dst, void* stream) {
+    clear_error();
+    if (!views || !d_dst || n_images <= 0) {
+        set_error("phd_convert_yuv_device: bad arguments");
+        return -1;
+    }
+    for (int i = 0; i < n_images; i++) {
+        std::string why;
+        if (!d_dst[i]) why = "destination is NULL";
+        if (!why.empty() || !yuv_view_why(views[i], &why)) {
+            set_error("image " + std::to_string(i) + ": " + why);
+            return -1;
+        }
+    }
+    Context* c = get_context();
+    if (!c) return -1;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const hipStream_t st = work_stream(c, stream);
+    if (!enqueue_yuv_views(c, views, d_dst, n_images, st)) return -1;
+    if (!stream) {
+        const hipError_t e = hipStreamSynchronize(st);
+        if (e != hipSuccess) {
+            set_error(std::string("phd_convert_yuv_device: ") + hipGetErrorString(e));
             return -1;
         }
         c->prof.collect();

@@ -19,6 +19,7 @@
 #include "batch_plan.h"
 #include "sharp_plan.h"
 #include "views_plan.h"
+#include "yuv_plan.h"
 
 namespace phd {
 
@@ -132,9 +133,10 @@ bool gfft_run(const GfftPlan& p, const double2* in, double2* out, long count, do
 // ---- per-kernel event timing (opt-in, phd_profile_kernels) -----------------
 enum KernelId {
     kK1 = 0, kFftRows = 1, kFftCols = 2, kCutoffs = 3, kPalSums = 4, kSharp = 5, kPack = 6, kClassify = 7,
-    kDecode = 8, kNumKernels = 9
+    kDecode = 8, kYuv = 9, kNumKernels = 10
 };
 static_assert(kClassify == kProfClassify && kDecode == kProfDecode, "the decode launches' profiler slots");
+static_assert(kYuv == kProfYuv, "the YUV conversion launch's profiler slot");
 struct KernelProfiler {
     unsigned mask = 0;                              // kernels to bracket with events
     // mask bits 24-30: stride s > 1, only every s-th batch call is bracketed
@@ -231,7 +233,9 @@ struct Context {
     size_t h_sharp_bytes = 0;
     // image views (views_plan.h): the packed staging images of one run, the
     // device table of the pack launch and its pinned copy; ev_views follows
-    // the last pack launch (the table is rewritten only after it)
+    // the last pack launch (the table is rewritten only after it).  The YUV
+    // views' conversion launch (yuv_plan.h) stages into d_vstage and keeps its
+    // table in d_views / h_views in the same way
     uint8_t* d_vstage = nullptr;
     size_t vstage_bytes = 0;
     void* d_views = nullptr;
@@ -428,6 +432,11 @@ bool enqueue_sharpness(Context* c, const uint8_t* const* d_imgs, int n, int widt
 // one read in place).  The table goes up through the context's pinned copy;
 // the launch is followed by c->ev_views.  views: validated (view_why).
 bool enqueue_pack_views(Context* c, const phd_image_view* views, uint8_t* const* dst, int n, hipStream_t st);
+// The conversion launch of a call's YUV views on st (yuv_views.hip): view i
+// goes to dst[i] (3 * height * width bytes).  The table goes through d_views /
+// h_views as the pack launch's does and the launch is followed by
+// c->ev_views.  views: validated (yuv_view_why).
+bool enqueue_yuv_views(Context* c, const phd_yuv_view* views, uint8_t* const* dst, int n, hipStream_t st);
 // The classify launch of a group's typed views on st (decode_views.hip): view
 // i's packed RGB8 image goes to dst[i] (3 * height * width bytes), its flag
 // word (kDecNotU8 | kDecNonFinite, decode_view.h) to flags[i] on the host.  The

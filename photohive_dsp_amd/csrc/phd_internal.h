@@ -428,6 +428,14 @@ hipError_t launch_classify_views(const DecodeRec* d_recs, int* d_flags, int n, i
                                  KernelProfiler* prof = nullptr);
 hipError_t launch_decode_view(const DecodeRec& rec, hipStream_t st, KernelProfiler* prof = nullptr);
 
+// ---- YCbCr views (yuv_views.hip, yuv_view.h) ----------------------------------
+// The conversion of n views (d_recs: the device table) in one launch over
+// (row band, view); max_bands: the most bands of one view.  n <= 65535 (grid.y).
+struct YuvRec;
+constexpr int kProfYuv = 9;
+hipError_t launch_yuv_views(const YuvRec* d_recs, int n, int max_bands, hipStream_t st,
+                            KernelProfiler* prof = nullptr);
+
 // ---- fp64 planar input of the legacy entry point (planar.hip) ---------------
 struct PlanarSrc {
     const double* r;

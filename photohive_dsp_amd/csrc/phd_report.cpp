@@ -5,6 +5,7 @@
 // same-size device images on one stream:
 //
 //   K0  gather of non-packed views    views calls only   (pack_views.hip)
+//       YCbCr -> RGB8 conversion      YUV calls only     (yuv_views.hip)
 //   K1  hsv/stats/histogram           every image        (palette.hip)
 //   D2H group histograms + moments    -> host decisions  (phd_palette.cpp)
 //   K4  FFT rows, K5 FFT columns      every image        (fft.hip)   || host decides
@@ -155,6 +156,32 @@ bool enqueue_pack_views(Context* c, const phd_image_view* views, uint8_t* const*
     for (size_t k = 0; k < recs.size(); k += kPackMaxViews) {
         const int m = (int)std::min<size_t>(kPackMaxViews, recs.size() - k);
         PHD_HIP(launch_pack_views((const PackRec*)c->d_views + k, m, max_bands, st, &c->prof));
+    }
+    PHD_HIP(hipEventRecord(c->ev_views, st));
+    return true;
+}
+
+bool enqueue_yuv_views(Context* c, const phd_yuv_view* views, uint8_t* const* dst, int n, hipStream_t st) {
+    if (n <= 0) return true;
+    std::vector<YuvRec> recs(n);
+    int max_bands = 0;
+    for (int i = 0; i < n; i++) {
+        recs[i] = yuv_record(views[i], dst[i]);
+        max_bands = std::max(max_bands, (recs[i].height + recs[i].band_rows - 1) / recs[i].band_rows);
+    }
+    // the table of the last pack, classify or conversion launch is still read until that launch is done
+    if (!c->ev_views) PHD_HIP(hipEventCreateWithFlags(&c->ev_views, hipEventDisableTiming));
+    else PHD_HIP(hipEventSynchronize(c->ev_views));
+    const size_t bytes = sizeof(YuvRec) * recs.size();
+    if (!ensure_device(&c->d_views, &c->views_bytes, bytes)) return false;
+    if (!grow_pinned(&c->h_views, &c->h_views_bytes, bytes)) return false;
+    memcpy(c->h_views, recs.data(), bytes);
+    PHD_HIP(hipMemcpyAsync(c->d_views, c->h_views, bytes, hipMemcpyHostToDevice, st));
+    // (grid.y = view: at most kYuvMaxViews a launch)
+    constexpr int kYuvMaxViews = 32768;
+    for (size_t k = 0; k < recs.size(); k += kYuvMaxViews) {
+        const int m = (int)std::min<size_t>(kYuvMaxViews, recs.size() - k);
+        PHD_HIP(launch_yuv_views((const YuvRec*)c->d_views + k, m, max_bands, st, &c->prof));
     }
     PHD_HIP(hipEventRecord(c->ev_views, st));
     return true;

@@ -4,7 +4,7 @@ import ctypes
 import os
 
 from .structures import (Blur_Profile, Blur_Vector, Crop_Boundaries, Full_Report_Data, Image_PGM, Image_RGB,
-                         PhdConfig, PhdImageView, PhdTypedView, RGB_Statistics)
+                         PhdConfig, PhdImageView, PhdTypedView, PhdYuvView, RGB_Statistics)
 
 def _preload_torch_hip_runtime():
     """One HIP runtime per process.  PyTorch-ROCm ships its own libamdhip64.so
@@ -113,6 +113,7 @@ KERNELS = ["hsv_stats", "fft_rows", "fft_cols", "palette_cutoffs", "palette_sums
 PACK_VIEWS_KERNEL = 6      # the image views' gather (bit 6 of phd_profile_kernels: "pack_views")
 CLASSIFY_VIEWS_KERNEL = 7  # the typed views' classifier (bit 7: "classify_views")
 DECODE_VIEWS_KERNEL = 8    # the typed views' decode to double planes (bit 8: "decode_views")
+YUV_VIEWS_KERNEL = 9       # the YCbCr views' conversion to RGB8 (bit 9: "yuv_views")
 lib.phd_debug_time_kernel.restype = ctypes.c_int
 lib.phd_debug_time_kernel.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, P(PhdConfig),
                                       ctypes.c_int, ctypes.c_int, P(ctypes.c_double)]
@@ -171,7 +172,14 @@ for _name, _res, _args in (("phd_shutdown", None, []),
                            ("phd_decode_views_device", ctypes.c_int,
                             [P(PhdTypedView), ctypes.c_int, P(ctypes.c_void_p), ctypes.c_void_p]),
                            ("phd_debug_decode_view_host", ctypes.c_int,
-                            [P(PhdTypedView), ctypes.c_void_p, ctypes.c_void_p, P(ctypes.c_int)])):
+                            [P(PhdTypedView), ctypes.c_void_p, ctypes.c_void_p, P(ctypes.c_int)]),
+                           # device YCbCr frames (views: n PhdYuvView)
+                           ("phd_report_batch_device_yuv", ctypes.c_int,
+                            [P(PhdYuvView), ctypes.c_int, P(PhdConfig), P(P(Crop_Boundaries)),
+                             P(P(Full_Report_Data)), P(ctypes.c_int), ctypes.c_void_p]),
+                           ("phd_convert_yuv_device", ctypes.c_int,
+                            [P(PhdYuvView), ctypes.c_int, P(ctypes.c_void_p), ctypes.c_void_p]),
+                           ("phd_debug_yuv_view_host", ctypes.c_int, [P(PhdYuvView), ctypes.c_void_p])):
     try:
         _f = getattr(lib, _name)
     except AttributeError:

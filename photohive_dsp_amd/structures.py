@@ -91,6 +91,22 @@ class PhdTypedView(Structure):
                 ("elem", c_int), ("flags", c_int), ("max_value", c_double)]
 
 
+class PhdYuvView(Structure):
+    """One device-resident 8-bit YCbCr frame (include/photohive_dsp.h: phd_yuv_view): luma of
+    pixel (y, x) is the byte at y + y*y_row_stride + x*y_pixel_stride, chroma sample (j, i)
+    the byte at cb (or cr) + j*c_row_stride + i*c_pixel_stride."""
+    _fields_ = [("y", c_void_p), ("cb", c_void_p), ("cr", c_void_p), ("height", c_int), ("width", c_int),
+                ("y_row_stride", c_int64), ("y_pixel_stride", c_int64),
+                ("c_row_stride", c_int64), ("c_pixel_stride", c_int64),
+                ("chroma_shift_x", c_int), ("chroma_shift_y", c_int),
+                ("matrix", c_int), ("range", c_int), ("chroma", c_int)]
+
+
+# phd_yuv_view.matrix, .range and .chroma
+PHD_YUV_BT601, PHD_YUV_BT709 = range(2)
+PHD_YUV_FULL, PHD_YUV_LIMITED = range(2)
+PHD_YUV_CHROMA_REPLICATE, PHD_YUV_CHROMA_TRIANGLE = range(2)
+
 # phd_typed_view.elem and .flags
 PHD_ELEM_U8, PHD_ELEM_U16, PHD_ELEM_F16, PHD_ELEM_F32, PHD_ELEM_F64 = range(5)
 PHD_VIEW_SNAP_U8 = 1
