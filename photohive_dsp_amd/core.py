@@ -240,6 +240,43 @@ def get_reports(images, salient_characters=None, **kw):
     return [(_finish(outs[i], hs[i], ws[i], kw) if st[i] == 0 else None) for i in range(n)]
 
 
+def _run_reports(call, name, n, sizes, kw):
+    """The result tail of the report*_device* wrappers: call(outs, status) makes
+    the C call over n images, sizes[i] is image i's (height, width).  The
+    reports, or RuntimeError with the library's message when one is missing."""
+    outs = (POINTER(Full_Report_Data) * n)()
+    st = (ctypes.c_int * n)()
+    call(outs, st)
+    res = [(_finish(outs[i], *sizes[i], kw) if st[i] == 0 else None) for i in range(n)]
+    if any(r is None for r in res):
+        err = last_error()
+        del res                     # (the reports that did come back are freed)
+        raise RuntimeError(f"{name} failed: {err}")
+    return res
+
+
+def _view_sizes(views, n):
+    return [(views[i].height, views[i].width) for i in range(n)]
+
+
+def _convert(call, name, views, n, shape, dtype, devices):
+    """The conversion-only wrappers: one new tensor of shape(height, width) per
+    view on devices[i], filled by call(array of their data pointers)."""
+    import torch
+    if n == 0:
+        return []
+    out = [torch.empty(shape(views[i].height, views[i].width), dtype=dtype, device=devices[i]) for i in range(n)]
+    dst = (ctypes.c_void_p * n)(*[o.data_ptr() for o in out])
+    if call(dst) != 0:
+        raise RuntimeError(f"{name} failed: {last_error()}")
+    return out
+
+
+def _tensor_devices(keep):
+    import torch
+    return [t.device if isinstance(t, torch.Tensor) else "cuda" for t in keep]
+
+
 def report_device(images, stream=None, salient_characters=None, **kw):
     """Reports for a uint8 torch tensor [N, H, W, 3] resident on the current GPU.
     salient_characters: per-image crop boxes (normalize_salient)."""
@@ -248,17 +285,15 @@ def report_device(images, stream=None, salient_characters=None, **kw):
     n, h, w = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
     cfg = make_config(**kw)
     crops = normalize_salient(salient_characters, n)
-    outs = (POINTER(Full_Report_Data) * n)()
-    st = (ctypes.c_int * n)()
     s = _stream_handle(stream)
-    if crops is None:
-        lib.phd_report_batch_device(images.data_ptr(), n, h, w, 0, ctypes.byref(cfg), outs, st, s)
-    else:
-        lib.phd_report_batch_device_crops(images.data_ptr(), n, h, w, 0, ctypes.byref(cfg), crops[0], outs, st, s)
-    res = [(_finish(outs[i], h, w, kw) if st[i] == 0 else None) for i in range(n)]
-    if any(r is None for r in res):
-        raise RuntimeError(f"report_device failed: {last_error()}")
-    return res
+
+    def call(outs, st):
+        if crops is None:
+            lib.phd_report_batch_device(images.data_ptr(), n, h, w, 0, ctypes.byref(cfg), outs, st, s)
+        else:
+            lib.phd_report_batch_device_crops(images.data_ptr(), n, h, w, 0, ctypes.byref(cfg), crops[0], outs, st, s)
+
+    return _run_reports(call, "report_device", n, [(h, w)] * n, kw)
 
 
 def reports_device_mixed(images, stream=None, salient_characters=None, **kw):
@@ -275,17 +310,56 @@ def reports_device_mixed(images, stream=None, salient_characters=None, **kw):
     ptrs = (ctypes.c_void_p * n)(*[im.data_ptr() for im in images])
     hs = (ctypes.c_int * n)(*[int(im.shape[0]) for im in images])
     ws = (ctypes.c_int * n)(*[int(im.shape[1]) for im in images])
-    outs = (POINTER(Full_Report_Data) * n)()
-    st = (ctypes.c_int * n)()
     s = _stream_handle(stream)
-    if crops is None:
-        lib.phd_report_batch_device_mixed(ptrs, hs, ws, n, ctypes.byref(cfg), outs, st, s)
+
+    def call(outs, st):
+        if crops is None:
+            lib.phd_report_batch_device_mixed(ptrs, hs, ws, n, ctypes.byref(cfg), outs, st, s)
+        else:
+            lib.phd_report_batch_device_mixed_crops(ptrs, hs, ws, n, ctypes.byref(cfg), crops[0], outs, st, s)
+
+    return _run_reports(call, "reports_device_mixed", n, list(zip(hs, ws)), kw)
+
+
+def _report_views(entry, name, views, n, stream, salient_characters, kw):
+    """reports_device_views, _typed and _yuv after their descriptors are made."""
+    cfg = make_config(**kw)
+    crops = normalize_salient(salient_characters, n)
+    s = _stream_handle(stream)
+    return _run_reports(lambda outs, st: entry(views, n, ctypes.byref(cfg), crops[0] if crops else None, outs, st, s),
+                        name, n, _view_sizes(views, n), kw)
+
+
+def _image_list(tensors, layout):
+    """make_views' and make_typed_views' input as a list of images."""
+    import torch
+    if layout not in ("HWC", "CHW"):
+        raise ValueError(f"layout must be 'HWC' or 'CHW', not {layout!r}")
+    if isinstance(tensors, torch.Tensor):
+        if tensors.dim() != 4:
+            raise ValueError("a single tensor must be 4-D (a batch of images)")
+        tensors = list(tensors.unbind(0))
+    return list(tensors)
+
+
+def _tensor_view_fields(t, layout, bgr, i):
+    """(data, height, width, row stride, pixel stride, channel stride), the
+    strides in bytes, of image i's tensor ([H, W, C] or [C, H, W], C = 3 or 4);
+    bgr: data at channel 2, the channel stride negated."""
+    if t.dim() != 3:
+        raise ValueError(f"image {i}: expected 3 dimensions ({layout}), got {t.dim()}")
+    if layout == "HWC":
+        (h, w, ch), (rs, ps, cs) = t.shape, t.stride()
     else:
-        lib.phd_report_batch_device_mixed_crops(ptrs, hs, ws, n, ctypes.byref(cfg), crops[0], outs, st, s)
-    res = [(_finish(outs[i], hs[i], ws[i], kw) if st[i] == 0 else None) for i in range(n)]
-    if any(r is None for r in res):
-        raise RuntimeError(f"reports_device_mixed failed: {last_error()}")
-    return res
+        (ch, h, w), (cs, rs, ps) = t.shape, t.stride()
+    if ch not in (3, 4):
+        raise ValueError(f"image {i}: expected 3 or 4 channels, got {ch}")
+    es = t.element_size()
+    rs, ps, cs = rs * es, ps * es, cs * es
+    data = t.data_ptr()
+    if bgr:
+        data, cs = data + 2 * cs, -cs
+    return data, int(h), int(w), int(rs), int(ps), int(cs)
 
 
 def make_views(tensors, layout="HWC", bgr=False):
@@ -299,13 +373,7 @@ def make_views(tensors, layout="HWC", bgr=False):
     Returns (array of PhdImageView, objects to keep alive while the views are
     in use)."""
     import torch
-    if layout not in ("HWC", "CHW"):
-        raise ValueError(f"layout must be 'HWC' or 'CHW', not {layout!r}")
-    if isinstance(tensors, torch.Tensor):
-        if tensors.dim() != 4:
-            raise ValueError("a single tensor must be 4-D (a batch of images)")
-        tensors = list(tensors.unbind(0))
-    tensors = list(tensors)
+    tensors = _image_list(tensors, layout)
     views = (PhdImageView * max(1, len(tensors)))()
     for i, t in enumerate(tensors):
         if isinstance(t, PhdImageView):
@@ -313,18 +381,7 @@ def make_views(tensors, layout="HWC", bgr=False):
             continue
         if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
             raise ValueError(f"image {i}: expected a uint8 torch tensor")
-        if t.dim() != 3:
-            raise ValueError(f"image {i}: expected 3 dimensions ({layout}), got {t.dim()}")
-        if layout == "HWC":
-            (h, w, ch), (rs, ps, cs) = t.shape, t.stride()
-        else:
-            (ch, h, w), (cs, rs, ps) = t.shape, t.stride()
-        if ch not in (3, 4):
-            raise ValueError(f"image {i}: expected 3 or 4 channels, got {ch}")
-        data = t.data_ptr()                      # uint8: element strides are byte strides
-        if bgr:
-            data, cs = data + 2 * cs, -cs
-        views[i] = PhdImageView(data, int(h), int(w), int(rs), int(ps), int(cs))
+        views[i] = PhdImageView(*_tensor_view_fields(t, layout, bgr, i))
     return views, tensors
 
 
@@ -337,17 +394,8 @@ def reports_device_views(images, layout="HWC", bgr=False, stream=None, salient_c
     salient_characters: per-image crop boxes in each view's own coordinates
     (normalize_salient)."""
     views, keep = make_views(images, layout, bgr)
-    n = len(keep)
-    cfg = make_config(**kw)
-    crops = normalize_salient(salient_characters, n)
-    outs = (POINTER(Full_Report_Data) * n)()
-    st = (ctypes.c_int * n)()
-    s = _stream_handle(stream)
-    lib.phd_report_batch_device_views(views, n, ctypes.byref(cfg), crops[0] if crops else None, outs, st, s)
-    res = [(_finish(outs[i], views[i].height, views[i].width, kw) if st[i] == 0 else None) for i in range(n)]
-    if any(r is None for r in res):
-        raise RuntimeError(f"reports_device_views failed: {last_error()}")
-    return res
+    return _report_views(lib.phd_report_batch_device_views, "reports_device_views", views, len(keep), stream,
+                         salient_characters, kw)
 
 
 def pack_views_device(images, layout="HWC", bgr=False, stream=None):
@@ -357,14 +405,8 @@ def pack_views_device(images, layout="HWC", bgr=False, stream=None):
     import torch
     views, keep = make_views(images, layout, bgr)
     n = len(keep)
-    if n == 0:
-        return []
-    out = [torch.empty((views[i].height, views[i].width, 3), dtype=torch.uint8,
-                       device=keep[i].device if isinstance(keep[i], torch.Tensor) else "cuda") for i in range(n)]
-    dst = (ctypes.c_void_p * n)(*[o.data_ptr() for o in out])
-    if lib.phd_pack_views_device(views, n, dst, _stream_handle(stream)) != 0:
-        raise RuntimeError(f"pack_views_device failed: {last_error()}")
-    return out
+    return _convert(lambda dst: lib.phd_pack_views_device(views, n, dst, _stream_handle(stream)),
+                    "pack_views_device", views, n, lambda h, w: (h, w, 3), torch.uint8, _tensor_devices(keep))
 
 
 def _typed_elems():
@@ -391,13 +433,7 @@ def make_typed_views(tensors, layout="HWC", bgr=False, max_value=None, snap_u8=F
     that is a PhdTypedView already is taken as it is.  Needs no GPU (CPU tensors
     work).  Returns (array of PhdTypedView, objects to keep alive)."""
     import torch
-    if layout not in ("HWC", "CHW"):
-        raise ValueError(f"layout must be 'HWC' or 'CHW', not {layout!r}")
-    if isinstance(tensors, torch.Tensor):
-        if tensors.dim() != 4:
-            raise ValueError("a single tensor must be 4-D (a batch of images)")
-        tensors = list(tensors.unbind(0))
-    tensors = list(tensors)
+    tensors = _image_list(tensors, layout)
     n = len(tensors)
     maxes = list(max_value) if isinstance(max_value, (list, tuple)) else [max_value] * n
     snaps = list(snap_u8) if isinstance(snap_u8, (list, tuple)) else [snap_u8] * n
@@ -411,24 +447,11 @@ def make_typed_views(tensors, layout="HWC", bgr=False, max_value=None, snap_u8=F
             continue
         if not isinstance(t, torch.Tensor) or t.dtype not in elems:
             raise ValueError(f"image {i}: expected a uint8, uint16, float16, float32 or float64 torch tensor")
-        if t.dim() != 3:
-            raise ValueError(f"image {i}: expected 3 dimensions ({layout}), got {t.dim()}")
-        if layout == "HWC":
-            (h, w, ch), (rs, ps, cs) = t.shape, t.stride()
-        else:
-            (ch, h, w), (cs, rs, ps) = t.shape, t.stride()
-        if ch not in (3, 4):
-            raise ValueError(f"image {i}: expected 3 or 4 channels, got {ch}")
-        es = t.element_size()
-        rs, ps, cs = rs * es, ps * es, cs * es
-        data = t.data_ptr()
-        if bgr:
-            data, cs = data + 2 * cs, -cs
+        fields = _tensor_view_fields(t, layout, bgr, i)
         mv = 0.0 if maxes[i] is None else float(maxes[i])
         if not (mv >= 0.0 and mv != float("inf")) or (maxes[i] is not None and mv == 0.0):
             raise ValueError(f"image {i}: max_value must be finite and positive")
-        views[i] = PhdTypedView(data, int(h), int(w), int(rs), int(ps), int(cs), elems[t.dtype],
-                                PHD_VIEW_SNAP_U8 if snaps[i] else 0, mv)
+        views[i] = PhdTypedView(*fields, elems[t.dtype], PHD_VIEW_SNAP_U8 if snaps[i] else 0, mv)
     return views, tensors
 
 
@@ -444,19 +467,8 @@ def reports_device_typed(images, layout="HWC", bgr=False, max_value=None, snap_u
     of pixels (phd_report_batch_device_typed_views).  salient_characters:
     per-image crop boxes in each view's own coordinates (normalize_salient)."""
     views, keep = make_typed_views(images, layout, bgr, max_value, snap_u8)
-    n = len(keep)
-    cfg = make_config(**kw)
-    crops = normalize_salient(salient_characters, n)
-    outs = (POINTER(Full_Report_Data) * n)()
-    st = (ctypes.c_int * n)()
-    s = _stream_handle(stream)
-    lib.phd_report_batch_device_typed_views(views, n, ctypes.byref(cfg), crops[0] if crops else None, outs, st, s)
-    res = [(_finish(outs[i], views[i].height, views[i].width, kw) if st[i] == 0 else None) for i in range(n)]
-    if any(r is None for r in res):
-        err = last_error()
-        del res                     # (the reports that did come back are freed)
-        raise RuntimeError(f"reports_device_typed failed: {err}")
-    return res
+    return _report_views(lib.phd_report_batch_device_typed_views, "reports_device_typed", views, len(keep), stream,
+                         salient_characters, kw)
 
 
 def decode_views_device(images, layout="HWC", bgr=False, max_value=None, stream=None):
@@ -466,14 +478,8 @@ def decode_views_device(images, layout="HWC", bgr=False, max_value=None, stream=
     import torch
     views, keep = make_typed_views(images, layout, bgr, max_value)
     n = len(keep)
-    if n == 0:
-        return []
-    out = [torch.empty((3, views[i].height, views[i].width), dtype=torch.float64,
-                       device=keep[i].device if isinstance(keep[i], torch.Tensor) else "cuda") for i in range(n)]
-    dst = (ctypes.c_void_p * n)(*[o.data_ptr() for o in out])
-    if lib.phd_decode_views_device(views, n, dst, _stream_handle(stream)) != 0:
-        raise RuntimeError(f"decode_views_device failed: {last_error()}")
-    return out
+    return _convert(lambda dst: lib.phd_decode_views_device(views, n, dst, _stream_handle(stream)),
+                    "decode_views_device", views, n, lambda h, w: (3, h, w), torch.float64, _tensor_devices(keep))
 
 
 def nv12_planes(surface, height, width):
@@ -568,19 +574,8 @@ def reports_device_yuv(frames, matrix="bt601", full_range=True, chroma="replicat
     (phd_report_batch_device_yuv).  salient_characters: per-image crop boxes
     in luma coordinates (normalize_salient)."""
     views, keep = make_yuv_views(frames, matrix, full_range, chroma, swap_uv)
-    n = len(keep)
-    cfg = make_config(**kw)
-    crops = normalize_salient(salient_characters, n)
-    outs = (POINTER(Full_Report_Data) * n)()
-    st = (ctypes.c_int * n)()
-    s = _stream_handle(stream)
-    lib.phd_report_batch_device_yuv(views, n, ctypes.byref(cfg), crops[0] if crops else None, outs, st, s)
-    res = [(_finish(outs[i], views[i].height, views[i].width, kw) if st[i] == 0 else None) for i in range(n)]
-    if any(r is None for r in res):
-        err = last_error()
-        del res                     # (the reports that did come back are freed)
-        raise RuntimeError(f"reports_device_yuv failed: {err}")
-    return res
+    return _report_views(lib.phd_report_batch_device_yuv, "reports_device_yuv", views, len(keep), stream,
+                         salient_characters, kw)
 
 
 def convert_yuv_device(frames, matrix="bt601", full_range=True, chroma="replicate", swap_uv=False, stream=None):
@@ -590,18 +585,9 @@ def convert_yuv_device(frames, matrix="bt601", full_range=True, chroma="replicat
     import torch
     views, keep = make_yuv_views(frames, matrix, full_range, chroma, swap_uv)
     n = len(keep)
-    if n == 0:
-        return []
-
-    def device(f):
-        return f[0].device if isinstance(f, (tuple, list)) else "cuda"
-
-    out = [torch.empty((views[i].height, views[i].width, 3), dtype=torch.uint8, device=device(keep[i]))
-           for i in range(n)]
-    dst = (ctypes.c_void_p * n)(*[o.data_ptr() for o in out])
-    if lib.phd_convert_yuv_device(views, n, dst, _stream_handle(stream)) != 0:
-        raise RuntimeError(f"convert_yuv_device failed: {last_error()}")
-    return out
+    return _convert(lambda dst: lib.phd_convert_yuv_device(views, n, dst, _stream_handle(stream)),
+                    "convert_yuv_device", views, n, lambda h, w: (h, w, 3), torch.uint8,
+                    [f[0].device if isinstance(f, (tuple, list)) else "cuda" for f in keep])
 
 
 def sharpness_device(images, salient_characters, stream=None):

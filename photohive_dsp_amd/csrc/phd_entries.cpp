@@ -1,6 +1,8 @@
 // phd_entries.cpp -- the exported C-ABI report, statistics, blur and sharpness
 // entries: argument checks, uploads, grouping and lanes around the pipeline
-// (run_reports, phd_report.cpp).
+// (run_reports, phd_report.cpp), and the driver of every device batch
+// (run_device_batch).  The entries over views, typed views and YUV views and
+// their input stage: phd_inputs.cpp.
 #include <cstdio>
 #include <cstdlib>
 #include <unistd.h>
@@ -335,20 +337,6 @@ extern "C" int phd_blur_batch_device(const uint8_t* d_rgb, int n_images, int hei
     return rc[0] < 0 || rc[1] < 0 ? -1 : 0;
 }
 
-// The reports and statuses of one run of m images, and their way back to the
-// caller's arrays: result k belongs to the caller's image idx[k].
-struct RunResults {
-    std::vector<Full_Report_Data*> o;
-    std::vector<int> st;
-    explicit RunResults(size_t m) : o(m, nullptr), st(m, -1) {}
-    void scatter(const std::vector<int>& idx, Full_Report_Data** out, int* status) const {
-        for (size_t k = 0; k < idx.size(); k++) {
-            out[idx[k]] = o[k];
-            status[idx[k]] = st[k];
-        }
-    }
-};
-
 static int count_failures(const int* status, int n) {
     int fails = 0;
     for (int i = 0; i < n; i++) fails += status[i] != 0;
@@ -484,19 +472,11 @@ static std::vector<int> valid_box_images(const Crop_Boundaries* const* crops, co
     return keep;
 }
 
-// A kept image of a device batch call, in caller order.
-struct BatchImage {
-    int index;                       // the caller's
-    const uint8_t* ptr;              // the packed device image, or (ptr NULL)
-    const phd_image_view* view;      // its view, gathered on the lane unless packed already
-    int height, width;
-    const Crop_Boundaries* boxes;    // NULL: none
-    const phd_yuv_view* yuv = nullptr;   // a YCbCr frame, converted on the lane (ptr and view NULL)
-};
+namespace phd {
 
 // One group of a batch large enough for two lanes (two-lane calls on the
 // library's streams only): two groups in lane_split's proportion, one per lane.
-static void split_for_lanes(std::vector<std::vector<int>>* groups, void* stream) {
+void split_for_lanes(std::vector<std::vector<int>>* groups, void* stream) {
     if (groups->size() != 1 || (*groups)[0].size() < 16 || stream || lanes_setting() < 2) return;
     std::vector<int>& first = (*groups)[0];
     const int h = lane_split((int)first.size());
@@ -505,85 +485,72 @@ static void split_for_lanes(std::vector<std::vector<int>>* groups, void* stream)
     groups->push_back(std::move(second));
 }
 
-// The image pointers of a group of views: a packed view's own, the others'
-// staging images on the lane (256-byte steps, K1's aligned form), gathered by
-// one launch on the call's stream.  run_reports returns with its results on
-// the host, so the staging images are free for the lane's next group.
-static bool stage_views(Context* cl, const std::vector<BatchImage>& imgs, const std::vector<int>& grp, void* stream,
-                        const uint8_t** ptrs) {
-    const int gm = (int)grp.size(), height = imgs[grp[0]].height, width = imgs[grp[0]].width;
-    std::vector<phd_image_view> gv(gm);
-    std::vector<uint8_t*> dst(gm, nullptr);
-    const size_t step = (3 * (size_t)height * width + 255) & ~(size_t)255;
-    auto packed = [&](int k) {
-        return pack_kind(width, gv[k].row_stride, gv[k].pixel_stride, gv[k].channel_stride) == kPackPacked;
-    };
-    size_t staged = 0;
-    for (int k = 0; k < gm; k++) {
-        gv[k] = *imgs[grp[k]].view;
-        staged += !packed(k);
+// The groups of the kept images of a mixed-size call: 64 images a run, or as
+// many as 64 of the 12 MP headline size hold (small images: one run for a
+// whole size instead of one per 64, so the per-run launches, host round trip
+// and partly filled grids are paid a few times)
+std::vector<std::vector<int>> mixed_groups(const std::vector<BatchImage>& imgs) {
+    std::vector<int> hs, ws;
+    for (const BatchImage& im : imgs) {
+        hs.push_back(im.height);
+        ws.push_back(im.width);
     }
-    if (staged && !ensure_device((void**)&cl->d_vstage, &cl->vstage_bytes, staged * step)) return false;
-    size_t slot = 0;
-    for (int k = 0; k < gm; k++) {
-        if (!packed(k)) dst[k] = cl->d_vstage + slot++ * step;
-        ptrs[k] = packed(k) ? gv[k].data : dst[k];
-    }
-    // (the reference's size checks come first: a size it rejects is not gathered)
-    return precheck(height, width) && enqueue_pack_views(cl, gv.data(), dst.data(), gm, work_stream(cl, stream));
+    return size_groups(hs.data(), ws.data(), (int)imgs.size(), 64, 64L * 12000000L);
 }
 
-// The image pointers of a group of YUV views: every view's staging image on
-// the lane (256-byte steps), converted by one launch on the call's stream.
-static bool stage_yuv(Context* cl, const std::vector<BatchImage>& imgs, const std::vector<int>& grp, void* stream,
-                      const uint8_t** ptrs) {
-    const int gm = (int)grp.size(), height = imgs[grp[0]].height, width = imgs[grp[0]].width;
-    // (the reference's size checks come first: a size it rejects is not read)
-    if (!precheck(height, width)) return false;
-    const size_t step = (3 * (size_t)height * width + 255) & ~(size_t)255;
-    if (!ensure_device((void**)&cl->d_vstage, &cl->vstage_bytes, (size_t)gm * step)) return false;
-    std::vector<phd_yuv_view> gv(gm);
-    std::vector<uint8_t*> dst(gm);
-    for (int k = 0; k < gm; k++) {
-        gv[k] = *imgs[grp[k]].yuv;
-        dst[k] = cl->d_vstage + (size_t)k * step;
-        ptrs[k] = dst[k];
+void report_group(Context* cl, const std::vector<BatchImage>& imgs, const std::vector<int>& grp,
+                  const std::vector<int>& ks, const uint8_t* const* ptrs, bool boxes, const phd_config& cfg,
+                  void* stream, RunResults* r) {
+    const int m = (int)ks.size();
+    if (m == 0) return;
+    std::vector<const uint8_t*> rp(m);
+    std::vector<const Crop_Boundaries*> cr(m);
+    for (int q = 0; q < m; q++) {
+        rp[q] = ptrs[ks[q]];
+        cr[q] = imgs[grp[ks[q]]].boxes;
     }
-    return enqueue_yuv_views(cl, gv.data(), dst.data(), gm, work_stream(cl, stream));
+    RunResults rr(m);
+    run_reports(cl, rp.data(), m, imgs[grp[0]].height, imgs[grp[0]].width, cfg, nullptr, rr.o.data(), rr.st.data(),
+                (hipStream_t)stream, boxes ? cr.data() : nullptr);
+    for (int q = 0; q < m; q++) {
+        r->o[ks[q]] = rr.o[q];
+        r->st[ks[q]] = rr.st[q];
+    }
 }
 
-// Runs the groups (indices into imgs, one same-size run_reports call each) on
-// the lanes and returns the call's failure count.  Two lanes when there are
-// two or more groups on the library's streams: lane L starts with group L,
-// then each lane takes the next untaken group when it is done with its last.
-// boxes: the call has per-image crop boxes (imgs[].boxes, NULL entries allowed).
-static int run_device_batch(Context* c, const std::vector<BatchImage>& imgs,
-                            const std::vector<std::vector<int>>& groups, bool boxes, const phd_config& cfg,
-                            Full_Report_Data** out, int* status, int n_images, void* stream) {
+// Two lanes when there are two or more groups on the library's streams: lane
+// L starts with group L, then each lane takes the next untaken group when it
+// is done with its last.
+int run_device_batch(Context* c, const std::vector<BatchImage>& imgs, const std::vector<std::vector<int>>& groups,
+                     GroupFn run_group, bool boxes, const phd_config& cfg, Full_Report_Data** out, int* status,
+                     int n_images, void* stream) {
     std::atomic<size_t> taken{0};                             // groups taken past each lane's first
-    auto run_group = [&](Context* cl, const std::vector<int>& grp) {
-        const int gm = (int)grp.size();
-        std::vector<const uint8_t*> ptrs(gm);
-        std::vector<const Crop_Boundaries*> cr(gm);
-        std::vector<int> idx(gm);
-        for (int k = 0; k < gm; k++) {
-            ptrs[k] = imgs[grp[k]].ptr;
-            cr[k] = imgs[grp[k]].boxes;
-            idx[k] = imgs[grp[k]].index;
-        }
-        RunResults r(gm);
-        const BatchImage& first = imgs[grp[0]];
-        if (first.yuv ? stage_yuv(cl, imgs, grp, stream, ptrs.data())
-                      : first.view == nullptr || stage_views(cl, imgs, grp, stream, ptrs.data()))
-            run_reports(cl, ptrs.data(), gm, imgs[grp[0]].height, imgs[grp[0]].width, cfg, nullptr, r.o.data(),
-                        r.st.data(), (hipStream_t)stream, boxes ? cr.data() : nullptr);
-        r.scatter(idx, out, status);
-    };
     if (!groups.empty())
         on_lanes(c, groups.size() >= 2 && !stream, [&](Context* cl, int lane, int nl) {
-            for (size_t gi = lane; gi < groups.size(); gi = nl + taken.fetch_add(1)) run_group(cl, groups[gi]);
+            for (size_t gi = lane; gi < groups.size(); gi = nl + taken.fetch_add(1)) {
+                const std::vector<int>& grp = groups[gi];
+                RunResults r(grp.size());
+                std::vector<int> idx(grp.size());
+                for (size_t k = 0; k < grp.size(); k++) idx[k] = imgs[grp[k]].index;
+                run_group(cl, imgs, grp, boxes, cfg, stream, &r);
+                r.scatter(idx, out, status);
+            }
         });
     return count_failures(status, n_images);
+}
+
+}  // namespace phd
+
+// A group of packed device images: reported where they lie.
+static void run_packed_group(Context* cl, const std::vector<BatchImage>& imgs, const std::vector<int>& grp, bool boxes,
+                             const phd_config& cfg, void* stream, RunResults* r) {
+    std::vector<const uint8_t*> ptrs(grp.size());
+    std::vector<int> ks(grp.size());
+    for (size_t k = 0; k < grp.size(); k++) {
+        ptrs[k] = (const uint8_t*)imgs[grp[k]].src;
+        ks[k] = (int)k;
+    }
+    report_group(cl, imgs, grp, ks, ptrs.data(), boxes, cfg, stream, r);
 }
 
 // Same-size device images at a stride: all kept images are one run (never cut
@@ -605,10 +572,10 @@ static int report_same_size(const char* entry, const uint8_t* d_rgb, int n_image
     std::vector<std::vector<int>> groups(keep.empty() ? 0 : 1);
     for (int i : keep) {
         groups[0].push_back((int)imgs.size());
-        imgs.push_back({i, d_rgb + (size_t)i * stride, nullptr, height, width, crops ? crops[i] : nullptr});
+        imgs.push_back({i, BatchImage::kPacked, d_rgb + (size_t)i * stride, height, width, crops ? crops[i] : nullptr});
     }
     split_for_lanes(&groups, stream);
-    return run_device_batch(c, imgs, groups, crops != nullptr, *cfg, out, status, n_images, stream);
+    return run_device_batch(c, imgs, groups, run_packed_group, crops != nullptr, *cfg, out, status, n_images, stream);
 }
 
 extern "C" int phd_report_batch_device(const uint8_t* d_rgb, int n_images, int height, int width,
@@ -626,19 +593,6 @@ extern "C" int phd_report_batch_device_crops(const uint8_t* d_rgb, int n_images,
                             height, width, image_stride, cfg, crops, out, status, stream);
 }
 
-// The groups of the kept images of a mixed-size call: 64 images a run, or as
-// many as 64 of the 12 MP headline size hold (small images: one run for a
-// whole size instead of one per 64, so the per-run launches, host round trip
-// and partly filled grids are paid a few times)
-static std::vector<std::vector<int>> mixed_groups(const std::vector<BatchImage>& imgs) {
-    std::vector<int> hs, ws;
-    for (const BatchImage& im : imgs) {
-        hs.push_back(im.height);
-        ws.push_back(im.width);
-    }
-    return size_groups(hs.data(), ws.data(), (int)imgs.size(), 64, 64L * 12000000L);
-}
-
 // Device-resident images of any sizes (BASELINE config 5): one batched run
 // (K1, FFTs, palette tail, per-image read-back) per group of same-size images.
 // A single size group is not split across lanes.
@@ -654,8 +608,9 @@ static int report_mixed(const char* entry, const uint8_t* const* d_images, const
     if (!c) return -1;
     std::vector<BatchImage> imgs;
     for (int i : valid_box_images(crops, heights, widths, 0, 0, n_images, out, status))
-        imgs.push_back({i, d_images[i], nullptr, heights[i], widths[i], crops ? crops[i] : nullptr});
-    return run_device_batch(c, imgs, mixed_groups(imgs), crops != nullptr, *cfg, out, status, n_images, stream);
+        imgs.push_back({i, BatchImage::kPacked, d_images[i], heights[i], widths[i], crops ? crops[i] : nullptr});
+    return run_device_batch(c, imgs, mixed_groups(imgs), run_packed_group, crops != nullptr, *cfg, out, status,
+                            n_images, stream);
 }
 
 extern "C" int phd_report_batch_device_mixed(const uint8_t* const* d_images, const int* heights, const int* widths,
@@ -671,311 +626,6 @@ extern "C" int phd_report_batch_device_mixed_crops(const uint8_t* const* d_image
                                                    int* status, void* stream) {
     return report_mixed(crops ? "phd_report_batch_device_mixed_crops" : "phd_report_batch_device_mixed", d_images,
                         heights, widths, n_images, cfg, crops, out, status, stream);
-}
-
-// Device images as byte-strided views (the input of get_full_report_data,
-// src/interface.c:20-94, in the layouts GPU producers emit: pack_view.h): the
-// mixed call over views, a single size group split as a same-size batch.
-extern "C" int phd_report_batch_device_views(const phd_image_view* views, int n_images, const phd_config* cfg,
-                                             const Crop_Boundaries* const* crops, Full_Report_Data** out,
-                                             int* status, void* stream) {
-    clear_error();
-    if (!views || !cfg || !out || !status || n_images <= 0) {
-        set_error("phd_report_batch_device_views: bad arguments");
-        return -1;
-    }
-    // a bad view or bad boxes fail their image alone (the last message stays)
-    std::vector<BatchImage> imgs;
-    std::string bad;
-    for (int i = 0; i < n_images; i++) {
-        out[i] = nullptr;
-        status[i] = -1;
-        std::string why;
-        if (view_why(views[i], &why) && (!crops || crops_why(crops[i], views[i].height, views[i].width, &why)))
-            imgs.push_back({i, nullptr, &views[i], views[i].height, views[i].width, crops ? crops[i] : nullptr});
-        else bad = "image " + std::to_string(i) + ": " + why;
-    }
-    Context* c = get_context();
-    if (!c) return -1;
-    if (!bad.empty()) set_error(bad);
-    auto groups = mixed_groups(imgs);
-    split_for_lanes(&groups, stream);
-    return run_device_batch(c, imgs, groups, crops != nullptr, *cfg, out, status, n_images, stream);
-}
-
-extern "C" int phd_pack_views_device(const phd_image_view* views, int n_images, uint8_t* const* d_dst, void* stream) {
-    clear_error();
-    if (!views || !d_dst || n_images <= 0) {
-        set_error("phd_pack_views_device: bad arguments");
-        return -1;
-    }
-    for (int i = 0; i < n_images; i++) {
-        std::string why;
-        if (!d_dst[i]) why = "destination is NULL";
-        if (!why.empty() || !view_why(views[i], &why)) {
-            set_error("image " + std::to_string(i) + ": " + why);
-            return -1;
-        }
-    }
-    Context* c = get_context();
-    if (!c) return -1;
-    std::lock_guard<std::mutex> lk(c->mu);
-    const hipStream_t st = work_stream(c, stream);
-    if (!enqueue_pack_views(c, views, d_dst, n_images, st)) return -1;
-    if (!stream) {
-        const hipError_t e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            set_error(std::string("phd_pack_views_device: ") + hipGetErrorString(e));
-            return -1;
-        }
-        c->prof.collect();
-    }
-    return 0;
-}
-
-// Device YCbCr frames (the input of get_full_report_data, src/interface.c:20-94,
-// as decoders emit it: yuv_view.h): the views call over YUV views, each
-// converted into its lane's staging image.
-extern "C" int phd_report_batch_device_yuv(const phd_yuv_view* views, int n_images, const phd_config* cfg,
-                                           const Crop_Boundaries* const* crops, Full_Report_Data** out, int* status,
-                                           void* stream) {
-    clear_error();
-    if (!views || !cfg || !out || !status || n_images <= 0) {
-        set_error("phd_report_batch_device_yuv: bad arguments");
-        return -1;
-    }
-    // a bad view or bad boxes fail their image alone (the last message stays)
-    std::vector<BatchImage> imgs;
-    std::string bad;
-    for (int i = 0; i < n_images; i++) {
-        out[i] = nullptr;
-        status[i] = -1;
-        std::string why;
-        if (yuv_view_why(views[i], &why) && (!crops || crops_why(crops[i], views[i].height, views[i].width, &why)))
-            imgs.push_back({i, nullptr, nullptr, views[i].height, views[i].width, crops ? crops[i] : nullptr,
-                            &views[i]});
-        else bad = "image " + std::to_string(i) + ": " + why;
-    }
-    Context* c = get_context();
-    if (!c) return -1;
-    if (!bad.empty()) set_error(bad);
-    auto groups = mixed_groups(imgs);
-    split_for_lanes(&groups, stream);
-    return run_device_batch(c, imgs, groups, crops != nullptr, *cfg, out, status, n_images, stream);
-}
-
-extern "C" int phd_convert_yuv_device(const phd_yuv_view* views, int n_images, uint8_t* const* d_dst, void* stream) {
-    clear_error();
-    if (!views || !d_dst || n_images <= 0) {
-        set_error("phd_convert_yuv_device: bad arguments");
-        return -1;
-    }
-    for (int i = 0; i < n_images; i++) {
-        std::string why;
-        if (!d_dst[i]) why = "destination is NULL";
-        if (!why.empty() || !yuv_view_why(views[i], &why)) {
-            set_error("image " + std::to_string(i) + ": " + why);
-            return -1;
-        }
-    }
-    Context* c = get_context();
-    if (!c) return -1;
-    std::lock_guard<std::mutex> lk(c->mu);
-    const hipStream_t st = work_stream(c, stream);
-    if (!enqueue_yuv_views(c, views, d_dst, n_images, st)) return -1;
-    if (!stream) {
-        const hipError_t e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            set_error(std::string("phd_convert_yuv_device: ") + hipGetErrorString(e));
-            return -1;
-        }
-        c->prof.collect();
-    }
-    return 0;
-}
-
-// ---- typed views ---------------------------------------------------------------
-// One same-size group of a typed call on a lane.  tv[k]: the typed view of
-// imgs[k].  The classifier writes every non-U8 view's RGB8 image into the
-// lane's staging area and says which are 8-bit; those, with the U8 views
-// (gathered by the pack launch unless packed), are one run_reports call; each
-// other finite image is decoded into the lane's double planes and reported by
-// the fp64 planar pipeline (phd_planar.cpp), one at a time.
-static void run_typed_group(Context* cl, const std::vector<BatchImage>& imgs, const phd_typed_view* const* tv,
-                            const std::vector<int>& grp, bool boxes, const phd_config& cfg, void* stream,
-                            RunResults* r) {
-    const int gm = (int)grp.size(), height = imgs[grp[0]].height, width = imgs[grp[0]].width;
-    // (the reference's size checks come first: a size it rejects is not read)
-    if (!precheck(height, width)) {
-        set_error("image " + std::to_string(imgs[grp[gm - 1]].index) + ": " + phd_last_error());
-        return;
-    }
-    const hipStream_t st = work_stream(cl, stream);
-    const size_t step = (3 * (size_t)height * width + 255) & ~(size_t)255;
-    std::vector<phd_image_view> gv(gm);
-    std::vector<uint8_t*> pack_dst(gm, nullptr), cls_dst;
-    std::vector<phd_typed_view> cls_views;
-    std::vector<int> cls_k;                                   // the group's classified images
-    size_t staged = 0;
-    for (int k = 0; k < gm; k++) {
-        const phd_typed_view& v = *tv[grp[k]];
-        gv[k] = typed_as_u8_view(v);
-        if (!typed_is_u8_view(v)) cls_k.push_back(k);
-        staged += !typed_is_u8_view(v) ||
-                  pack_kind(width, gv[k].row_stride, gv[k].pixel_stride, gv[k].channel_stride) != kPackPacked;
-    }
-    // every allocation before the first launch that writes into it
-    const size_t n = (size_t)height * width;
-    if (staged && !ensure_device((void**)&cl->d_vstage, &cl->vstage_bytes, staged * step)) return;
-    std::vector<const uint8_t*> ptrs(gm, nullptr);
-    size_t slot = 0;
-    for (int k = 0; k < gm; k++) {
-        const bool u8 = typed_is_u8_view(*tv[grp[k]]);
-        if (u8 && pack_kind(width, gv[k].row_stride, gv[k].pixel_stride, gv[k].channel_stride) == kPackPacked) {
-            ptrs[k] = gv[k].data;
-            continue;
-        }
-        uint8_t* d = cl->d_vstage + slot++ * step;
-        ptrs[k] = d;
-        if (u8) pack_dst[k] = d;
-        else {
-            cls_dst.push_back(d);
-            cls_views.push_back(*tv[grp[k]]);
-        }
-    }
-    std::vector<int> flags(cls_k.size(), 0);
-    if (!classify_views(cl, cls_views.data(), cls_dst.data(), (int)cls_k.size(), st, flags.data())) return;
-    if (!enqueue_pack_views(cl, gv.data(), pack_dst.data(), gm, st)) return;
-    std::vector<int> route(gm, 0);                            // 0: RGB8 run, else the classifier's flags
-    for (size_t q = 0; q < cls_k.size(); q++) route[cls_k[q]] = flags[q];
-    // the RGB8 run
-    std::vector<int> run_k;
-    for (int k = 0; k < gm; k++)
-        if (!route[k]) run_k.push_back(k);
-    if (!run_k.empty()) {
-        const int m = (int)run_k.size();
-        std::vector<const uint8_t*> rp(m);
-        std::vector<const Crop_Boundaries*> cr(m);
-        for (int q = 0; q < m; q++) {
-            rp[q] = ptrs[run_k[q]];
-            cr[q] = imgs[grp[run_k[q]]].boxes;
-        }
-        RunResults rr(m);
-        run_reports(cl, rp.data(), m, height, width, cfg, nullptr, rr.o.data(), rr.st.data(), (hipStream_t)stream,
-                    boxes ? cr.data() : nullptr);
-        for (int q = 0; q < m; q++) {
-            r->o[run_k[q]] = rr.o[q];
-            r->st[run_k[q]] = rr.st[q];
-        }
-    }
-    // the fp64 images, one at a time; a failing image keeps its message (the last one stays)
-    std::string bad, why;
-    for (int k = 0; k < gm; k++) {
-        if (!route[k]) continue;
-        const std::string name = "image " + std::to_string(imgs[grp[k]].index) + ": ";
-        if (route[k] & kDecNonFinite) {
-            bad = name + "Error: channel values must be finite (NaN or infinity in the image).";
-            continue;
-        }
-        if (!validate_config(cfg, &why)) {
-            bad = name + why;
-            continue;
-        }
-        // (the stream is idle: the planes may move)
-        if (!ensure_device((void**)&cl->d_planes, &cl->planes_bytes, sizeof(double) * 4 * n)) {
-            bad = name + phd_last_error();
-            continue;
-        }
-        double* dp = cl->d_planes;
-        Full_Report_Data* o = nullptr;
-        if (enqueue_decode_view(cl, *tv[grp[k]], dp, st))
-            o = report_planes_device(cl, PlanarSrc{dp, dp + n, dp + 2 * n}, height, width, cfg,
-                                     boxes ? imgs[grp[k]].boxes : nullptr, st);
-        (void)hipStreamSynchronize(st);
-        cl->prof.collect();
-        if (o) {
-            r->o[k] = o;
-            r->st[k] = 0;
-        } else bad = name + phd_last_error();
-    }
-    if (!bad.empty()) set_error(bad);
-}
-
-// Device images of any element type as byte-strided views (the input of
-// get_full_report_data, src/interface.c:20-94, as the reference's Pixels,
-// src/types.h:5): the views call over typed views.
-extern "C" int phd_report_batch_device_typed_views(const phd_typed_view* views, int n_images, const phd_config* cfg,
-                                                   const Crop_Boundaries* const* crops, Full_Report_Data** out,
-                                                   int* status, void* stream) {
-    clear_error();
-    if (!views || !cfg || !out || !status || n_images <= 0) {
-        set_error("phd_report_batch_device_typed_views: bad arguments");
-        return -1;
-    }
-    // a bad view or bad boxes fail their image alone (the last message stays)
-    std::vector<BatchImage> imgs;
-    std::vector<const phd_typed_view*> tv;
-    std::string bad;
-    for (int i = 0; i < n_images; i++) {
-        out[i] = nullptr;
-        status[i] = -1;
-        std::string why;
-        if (typed_view_why(views[i], &why) &&
-            (!crops || crops_why(crops[i], views[i].height, views[i].width, &why))) {
-            imgs.push_back({i, nullptr, nullptr, views[i].height, views[i].width, crops ? crops[i] : nullptr});
-            tv.push_back(&views[i]);
-        } else bad = "image " + std::to_string(i) + ": " + why;
-    }
-    Context* c = get_context();
-    if (!c) return -1;
-    if (!bad.empty()) set_error(bad);
-    auto groups = mixed_groups(imgs);
-    split_for_lanes(&groups, stream);
-    std::atomic<size_t> taken{0};                             // groups taken past each lane's first
-    if (!groups.empty())
-        on_lanes(c, groups.size() >= 2 && !stream, [&](Context* cl, int lane, int nl) {
-            for (size_t gi = lane; gi < groups.size(); gi = nl + taken.fetch_add(1)) {
-                const std::vector<int>& grp = groups[gi];
-                RunResults r(grp.size());
-                std::vector<int> idx(grp.size());
-                for (size_t k = 0; k < grp.size(); k++) idx[k] = imgs[grp[k]].index;
-                run_typed_group(cl, imgs, tv.data(), grp, crops != nullptr, *cfg, stream, &r);
-                r.scatter(idx, out, status);
-            }
-        });
-    return count_failures(status, n_images);
-}
-
-extern "C" int phd_decode_views_device(const phd_typed_view* views, int n_images, double* const* d_planes,
-                                       void* stream) {
-    clear_error();
-    if (!views || !d_planes || n_images <= 0) {
-        set_error("phd_decode_views_device: bad arguments");
-        return -1;
-    }
-    for (int i = 0; i < n_images; i++) {
-        std::string why;
-        if (!d_planes[i]) why = "destination is NULL";
-        if (!why.empty() || !typed_view_why(views[i], &why)) {
-            set_error("image " + std::to_string(i) + ": " + why);
-            return -1;
-        }
-    }
-    Context* c = get_context();
-    if (!c) return -1;
-    std::lock_guard<std::mutex> lk(c->mu);
-    const hipStream_t st = work_stream(c, stream);
-    for (int i = 0; i < n_images; i++)
-        if (!enqueue_decode_view(c, views[i], d_planes[i], st)) return -1;
-    if (!stream) {
-        const hipError_t e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            set_error(std::string("phd_decode_views_device: ") + hipGetErrorString(e));
-            return -1;
-        }
-        c->prof.collect();
-    }
-    return 0;
 }
 
 extern "C" int phd_report_batch_u8_crops(const uint8_t* const* images, const int* heights, const int* widths,

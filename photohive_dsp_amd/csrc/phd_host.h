@@ -231,11 +231,10 @@ struct Context {
     size_t sharp_bytes = 0;
     void* h_sharp = nullptr;
     size_t h_sharp_bytes = 0;
-    // image views (views_plan.h): the packed staging images of one run, the
-    // device table of the pack launch and its pinned copy; ev_views follows
-    // the last pack launch (the table is rewritten only after it).  The YUV
-    // views' conversion launch (yuv_plan.h) stages into d_vstage and keeps its
-    // table in d_views / h_views in the same way
+    // the input stage (phd_inputs.cpp): the packed staging images of one run
+    // of views, typed views or YUV views, the device table of the pack,
+    // classify or conversion launch and its pinned copy; ev_views follows the
+    // last such launch (the table is rewritten only after it)
     uint8_t* d_vstage = nullptr;
     size_t vstage_bytes = 0;
     void* d_views = nullptr;
@@ -243,8 +242,7 @@ struct Context {
     void* h_views = nullptr;
     size_t h_views_bytes = 0;
     hipEvent_t ev_views = nullptr;
-    // typed views: the snap tables' device copy (views_plan.h: snap_tables); the
-    // classifier's table and flag words share d_views / h_views with the pack launch
+    // typed views: the snap tables' device copy (views_plan.h: snap_tables)
     uint8_t* d_snap = nullptr;
     hipEvent_t ev[8] = {};
     // two streams per context: `stream` (K1, then the FFT chain) and `tail`
@@ -427,24 +425,53 @@ bool run_reports(Context* c, const uint8_t* const* d_imgs, int n, int height, in
 // the context's own buffer (*flat_dev; plan slots must be flat).
 bool enqueue_sharpness(Context* c, const uint8_t* const* d_imgs, int n, int width, const SharpPlan& plan,
                        double* out0, long out_stride, hipStream_t st, double** flat_dev = nullptr);
-// The pack launch of a call's views on st (pack_views.hip): view i goes to
-// dst[i] (3 * height * width bytes; nullptr: the view is left out, as a packed
-// one read in place).  The table goes up through the context's pinned copy;
-// the launch is followed by c->ev_views.  views: validated (view_why).
-bool enqueue_pack_views(Context* c, const phd_image_view* views, uint8_t* const* dst, int n, hipStream_t st);
-// The conversion launch of a call's YUV views on st (yuv_views.hip): view i
-// goes to dst[i] (3 * height * width bytes).  The table goes through d_views /
-// h_views as the pack launch's does and the launch is followed by
-// c->ev_views.  views: validated (yuv_view_why).
-bool enqueue_yuv_views(Context* c, const phd_yuv_view* views, uint8_t* const* dst, int n, hipStream_t st);
-// The classify launch of a group's typed views on st (decode_views.hip): view
-// i's packed RGB8 image goes to dst[i] (3 * height * width bytes), its flag
-// word (kDecNotU8 | kDecNonFinite, decode_view.h) to flags[i] on the host.  The
-// table and the flag words go through d_views / h_views as the pack launch's
-// do; returns with the flags read back (st drained).  views: validated.
-bool classify_views(Context* c, const phd_typed_view* views, uint8_t* const* dst, int n, hipStream_t st, int* flags);
-// The decode launch of one validated view into planes (3 * height * width doubles) on st.
-bool enqueue_decode_view(Context* c, const phd_typed_view& view, double* planes, hipStream_t st);
+// A grow-only pinned block of at least `need` bytes (the old one is freed at once)
+bool grow_pinned(void** p, size_t* cap, size_t need);
+
+// ---- device batches (the driver: phd_entries.cpp; views, typed views and
+// ---- YUV views: phd_inputs.cpp) ------------------------------------------------
+// A kept image of a device batch call, in caller order.
+struct BatchImage {
+    enum Source { kPacked, kView, kTyped, kYuv };
+    int index;                       // the caller's
+    Source kind;
+    const void* src;                 // the packed RGB8 device image, or the caller's phd_image_view,
+                                     // phd_typed_view or phd_yuv_view of it (staged on the lane)
+    int height, width;
+    const Crop_Boundaries* boxes;    // NULL: none
+};
+// The reports and statuses of one run of m images, and their way back to the
+// caller's arrays: result k belongs to the caller's image idx[k].
+struct RunResults {
+    std::vector<Full_Report_Data*> o;
+    std::vector<int> st;
+    explicit RunResults(size_t m) : o(m, nullptr), st(m, -1) {}
+    void scatter(const std::vector<int>& idx, Full_Report_Data** out, int* status) const {
+        for (size_t k = 0; k < idx.size(); k++) {
+            out[idx[k]] = o[k];
+            status[idx[k]] = st[k];
+        }
+    }
+};
+// One same-size group (indices into imgs) on a lane: stages what its source
+// kind needs and reports it; r: the group's results, in the group's order.
+// boxes: the call has per-image crop boxes (imgs[].boxes, NULL entries allowed).
+using GroupFn = void (*)(Context* cl, const std::vector<BatchImage>& imgs, const std::vector<int>& grp, bool boxes,
+                         const phd_config& cfg, void* stream, RunResults* r);
+// One run_reports call over the group's images at positions ks (image grp[k]
+// packed at ptrs[k]); their results into r at those positions.
+void report_group(Context* cl, const std::vector<BatchImage>& imgs, const std::vector<int>& grp,
+                  const std::vector<int>& ks, const uint8_t* const* ptrs, bool boxes, const phd_config& cfg,
+                  void* stream, RunResults* r);
+// Runs the groups on the lanes (the only lane loop of the device entries) and
+// returns the call's failure count.
+int run_device_batch(Context* c, const std::vector<BatchImage>& imgs, const std::vector<std::vector<int>>& groups,
+                     GroupFn run_group, bool boxes, const phd_config& cfg, Full_Report_Data** out, int* status,
+                     int n_images, void* stream);
+// The same-size groups of the kept images of a mixed-size call, and one group
+// of a batch large enough for two lanes cut in two (views, typed and YUV calls)
+std::vector<std::vector<int>> mixed_groups(const std::vector<BatchImage>& imgs);
+void split_for_lanes(std::vector<std::vector<int>>* groups, void* stream);
 // Palette intermediates only (for parity tests).
 bool run_palette_trace(Context* c, const uint8_t* d_img, int height, int width, const phd_config& cfg,
                        std::vector<unsigned>* hist, PaletteDecision* dec,

@@ -16,7 +16,7 @@
 //
 // report_planar is the upload and the 8-bit test; report_planes_device is the
 // fp64 pipeline on planes that are on the device, which the typed views' entry
-// (phd_entries.cpp) also runs on the planes k_decode_view filled.
+// (phd_inputs.cpp) also runs on the planes k_decode_view filled.
 #include <cmath>
 #include <cstring>
 

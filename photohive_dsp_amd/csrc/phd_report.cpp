@@ -1,5 +1,5 @@
-// phd_report.cpp -- the report pipeline (its C-ABI entries: phd_entries.cpp;
-// report assembly: phd_assemble.cpp; hooks: phd_debug.cpp).
+// phd_report.cpp -- the report pipeline (its C-ABI entries: phd_entries.cpp
+// and phd_inputs.cpp; report assembly: phd_assemble.cpp; hooks: phd_debug.cpp).
 //
 // Stage order of get_full_report_data (src/interface.c:20-94), per batch of
 // same-size device images on one stream:
@@ -77,7 +77,9 @@ Layout make_layout(int n, int tl, int nchunks, int nbins, int ncrops, int ncolbl
     return L;
 }
 
-// A grow-only pinned block of at least `need` bytes (the old one is freed at once)
+}  // namespace
+
+// (phd_host.h; the sharpness box table here, the input stage's launch tables)
 bool grow_pinned(void** p, size_t* cap, size_t need) {
     if (*cap >= need) return true;
     if (*p) (void)hipHostFree(*p);
@@ -91,8 +93,6 @@ bool grow_pinned(void** p, size_t* cap, size_t need) {
     *cap = sz;
     return true;
 }
-
-}  // namespace
 
 // shared with the planar path (phd_planar.cpp)
 bool check_crops(const Crop_Boundaries* cb, int height, int width) {
@@ -129,109 +129,6 @@ bool enqueue_sharpness(Context* c, const uint8_t* const* d_imgs, int n, int widt
     PHD_HIP(launch_sharpness_batch((const uint8_t* const*)ds, (const SharpBox*)(ds + o_box), (const int*)(ds + o_pre),
                                    nb, nslices, width, c->d_k255, (SharpPart*)(ds + up), dst, out0 ? out_stride : 0,
                                    st, &c->prof));
-    return true;
-}
-
-bool enqueue_pack_views(Context* c, const phd_image_view* views, uint8_t* const* dst, int n, hipStream_t st) {
-    std::vector<PackRec> recs;
-    int max_bands = 0;
-    for (int i = 0; i < n; i++) {
-        if (!dst[i]) continue;
-        const PackRec r = pack_record(views[i], dst[i]);
-        recs.push_back(r);
-        max_bands = std::max(max_bands, (r.height + r.band_rows - 1) / r.band_rows);
-    }
-    if (recs.empty()) return true;
-    // the table of the last pack launch is still read until that launch is done
-    // (a caller's stream is not drained by the call that used it)
-    if (!c->ev_views) PHD_HIP(hipEventCreateWithFlags(&c->ev_views, hipEventDisableTiming));
-    else PHD_HIP(hipEventSynchronize(c->ev_views));
-    const size_t bytes = sizeof(PackRec) * recs.size();
-    if (!ensure_device(&c->d_views, &c->views_bytes, bytes)) return false;
-    if (!grow_pinned(&c->h_views, &c->h_views_bytes, bytes)) return false;
-    memcpy(c->h_views, recs.data(), bytes);
-    PHD_HIP(hipMemcpyAsync(c->d_views, c->h_views, bytes, hipMemcpyHostToDevice, st));
-    // (grid.y = view: at most kPackMaxViews a launch)
-    constexpr int kPackMaxViews = 32768;
-    for (size_t k = 0; k < recs.size(); k += kPackMaxViews) {
-        const int m = (int)std::min<size_t>(kPackMaxViews, recs.size() - k);
-        PHD_HIP(launch_pack_views((const PackRec*)c->d_views + k, m, max_bands, st, &c->prof));
-    }
-    PHD_HIP(hipEventRecord(c->ev_views, st));
-    return true;
-}
-
-bool enqueue_yuv_views(Context* c, const phd_yuv_view* views, uint8_t* const* dst, int n, hipStream_t st) {
-    if (n <= 0) return true;
-    std::vector<YuvRec> recs(n);
-    int max_bands = 0;
-    for (int i = 0; i < n; i++) {
-        recs[i] = yuv_record(views[i], dst[i]);
-        max_bands = std::max(max_bands, (recs[i].height + recs[i].band_rows - 1) / recs[i].band_rows);
-    }
-    // the table of the last pack, classify or conversion launch is still read until that launch is done
-    if (!c->ev_views) PHD_HIP(hipEventCreateWithFlags(&c->ev_views, hipEventDisableTiming));
-    else PHD_HIP(hipEventSynchronize(c->ev_views));
-    const size_t bytes = sizeof(YuvRec) * recs.size();
-    if (!ensure_device(&c->d_views, &c->views_bytes, bytes)) return false;
-    if (!grow_pinned(&c->h_views, &c->h_views_bytes, bytes)) return false;
-    memcpy(c->h_views, recs.data(), bytes);
-    PHD_HIP(hipMemcpyAsync(c->d_views, c->h_views, bytes, hipMemcpyHostToDevice, st));
-    // (grid.y = view: at most kYuvMaxViews a launch)
-    constexpr int kYuvMaxViews = 32768;
-    for (size_t k = 0; k < recs.size(); k += kYuvMaxViews) {
-        const int m = (int)std::min<size_t>(kYuvMaxViews, recs.size() - k);
-        PHD_HIP(launch_yuv_views((const YuvRec*)c->d_views + k, m, max_bands, st, &c->prof));
-    }
-    PHD_HIP(hipEventRecord(c->ev_views, st));
-    return true;
-}
-
-// the snap tables' device copy (uploaded once per context)
-static const uint8_t* device_snap(Context* c) {
-    if (c->d_snap) return c->d_snap;
-    uint8_t* d = nullptr;
-    if (hipMalloc((void**)&d, kSnapBytes) != hipSuccess ||
-        hipMemcpy(d, snap_tables(), kSnapBytes, hipMemcpyHostToDevice) != hipSuccess) {
-        if (d) (void)hipFree(d);
-        set_error("snap table upload failed");
-        return nullptr;
-    }
-    return c->d_snap = d;
-}
-
-bool classify_views(Context* c, const phd_typed_view* views, uint8_t* const* dst, int n, hipStream_t st, int* flags) {
-    if (n <= 0) return true;
-    const uint8_t* snap = device_snap(c);
-    if (!snap) return false;
-    std::vector<DecodeRec> recs(n);
-    int max_bands = 0;
-    for (int i = 0; i < n; i++) {
-        recs[i] = decode_record(views[i], nullptr, dst[i], snap);
-        max_bands = std::max(max_bands, (recs[i].height + recs[i].band_rows - 1) / recs[i].band_rows);
-    }
-    // the table of the last pack or classify launch is still read until that launch is done
-    if (!c->ev_views) PHD_HIP(hipEventCreateWithFlags(&c->ev_views, hipEventDisableTiming));
-    else PHD_HIP(hipEventSynchronize(c->ev_views));
-    // records | flag words (zero), one upload
-    const size_t o_flags = al(sizeof(DecodeRec) * (size_t)n), bytes = o_flags + sizeof(int) * (size_t)n;
-    if (!ensure_device(&c->d_views, &c->views_bytes, bytes)) return false;
-    if (!grow_pinned(&c->h_views, &c->h_views_bytes, bytes)) return false;
-    uint8_t* hv = (uint8_t*)c->h_views;
-    uint8_t* dv = (uint8_t*)c->d_views;
-    memset(hv, 0, bytes);
-    memcpy(hv, recs.data(), sizeof(DecodeRec) * (size_t)n);
-    PHD_HIP(hipMemcpyAsync(dv, hv, bytes, hipMemcpyHostToDevice, st));
-    PHD_HIP(launch_classify_views((const DecodeRec*)dv, (int*)(dv + o_flags), n, max_bands, st, &c->prof));
-    PHD_HIP(hipMemcpyAsync(hv + o_flags, dv + o_flags, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
-    PHD_HIP(hipEventRecord(c->ev_views, st));
-    PHD_HIP(hipStreamSynchronize(st));
-    memcpy(flags, hv + o_flags, sizeof(int) * (size_t)n);
-    return true;
-}
-
-bool enqueue_decode_view(Context* c, const phd_typed_view& view, double* planes, hipStream_t st) {
-    PHD_HIP(launch_decode_view(decode_record(view, planes, nullptr, nullptr), st, &c->prof));
     return true;
 }
 
