@@ -485,6 +485,17 @@ int phd_debug_hsv_groups_device(const uint8_t* d_rgb, long n_pixels, const phd_c
 int phd_debug_k1_pixels(const uint8_t* rgb, long n, const phd_config* cfg, int* cell, double* h, double* s,
                         int* deferred);
 
+/* Host only (no device needed): which palette kernels a full-resolution report
+ * of this configuration runs, as the library's own limits decide it.  -1 for a
+ * configuration the library rejects, else a mask: 1 the one-pass (fused)
+ * palette, else K1 histogram + Kcut + K3; 2 the table K1 runs word-aligned
+ * batches, 4 in its two-block form; 8 the saturation class comes from
+ * per-value thresholds (s_partitions <= 6), else from the table in global
+ * memory; 16 the grid has a K1 code table; 32 the palette's second pass of an
+ * image with max_slots palette slots is the batched one (one Kcut and one K3
+ * launch per batch), else one pair of launches per image. */
+int phd_debug_palette_path(const phd_config* cfg, int max_slots);
+
 /* Micro-benchmark hook: average ms per launch of one pipeline kernel (0 hsv_stats,
  * 1 fft_rows, 2 fft_cols) over `iters` launches on a device image; `ablate` is a
  * debug mask (0 = production kernel). */

@@ -1321,6 +1321,10 @@ __global__ __launch_bounds__(kThreads) void k_cutoffs(const uint8_t* __restrict_
 
 // K3: per-slot sums over the pixels each palette parent keeps
 // (calculate_avg_hsv, src/color_quantization.c:529-558): wrap(h + off), s, v, n.
+// kStage: the keep rules and slot offsets are staged in LDS beside the sums;
+// else (fine grids with thousands of slots, where the three do not fit the
+// CU's LDS together) they are read from global memory and LDS holds the sums.
+template <bool kStage>
 __global__ __launch_bounds__(kThreads) void k_palette_sums(const uint8_t* __restrict__ img, long npix,
                                                            int width, int ds, int nw, GridParams gp,
                                                            const GroupRule* __restrict__ rules_g,
@@ -1331,13 +1335,17 @@ __global__ __launch_bounds__(kThreads) void k_palette_sums(const uint8_t* __rest
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double* k255 = reinterpret_cast<double*>(smem);                       // 256
     double* acc = k255 + 256;                                              // nslots*4
-    double* off = acc + 4 * nslots;                                        // nslots
-    GroupRule* rules = reinterpret_cast<GroupRule*>(off + nslots);         // tl
+    double* off_l = acc + 4 * nslots;                                      // kStage: nslots
+    GroupRule* rules_l = reinterpret_cast<GroupRule*>(off_l + nslots);     // kStage: tl
     const int tid = threadIdx.x;
     k255[tid] = k255g[tid];
     for (int i = tid; i < 4 * nslots; i += kThreads) acc[i] = 0.0;
-    for (int i = tid; i < nslots; i += kThreads) off[i] = off_g[i];
-    for (int i = tid; i < gp.tl; i += kThreads) rules[i] = rules_g[i];
+    if (kStage) {
+        for (int i = tid; i < nslots; i += kThreads) off_l[i] = off_g[i];
+        for (int i = tid; i < gp.tl; i += kThreads) rules_l[i] = rules_g[i];
+    }
+    const double* off = kStage ? off_l : off_g;
+    const GroupRule* rules = kStage ? rules_l : rules_g;
     __syncthreads();
     const long base = (long)blockIdx.x * kChunk;
     const long end = min(base + (long)kChunk, npix);
@@ -1579,10 +1587,22 @@ hipError_t launch_palette_sums(const uint8_t* img, int height, int width, int ds
     int nw;
     const long n = hsv_pixels(height, width, ds, &nw);
     const int nchunks = (int)((n + kChunk - 1) / kChunk);
-    const size_t lds = sizeof(double) * (256 + 5 * (size_t)nslots) + sizeof(GroupRule) * gp.tl;
     const int aligned = (reinterpret_cast<uintptr_t>(img) & 3) == 0;
-    phd_launch(k_palette_sums, dim3(nchunks), dim3(kThreads), lds, st, img, n, width, ds, nw,
-                       gp, rules, slot_off, nslots, out, k255, aligned);
+    static const bool attr = ((void)hipFuncSetAttribute((const void*)k_palette_sums<true>,
+                                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
+                              (void)hipFuncSetAttribute((const void*)k_palette_sums<false>,
+                                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
+                              true);
+    (void)attr;
+    // the sums (<= 4096 slots: 130 KiB), and beside them the rules and slot offsets where all fit the LDS
+    const size_t lds_sums = sizeof(double) * (256 + 4 * (size_t)nslots);
+    const size_t lds_all = lds_sums + sizeof(double) * nslots + sizeof(GroupRule) * gp.tl;
+    if (lds_all <= 160 * 1024)
+        phd_launch(k_palette_sums<true>, dim3(nchunks), dim3(kThreads), lds_all, st, img, n, width, ds, nw,
+                           gp, rules, slot_off, nslots, out, k255, aligned);
+    else
+        phd_launch(k_palette_sums<false>, dim3(nchunks), dim3(kThreads), lds_sums, st, img, n, width, ds, nw,
+                           gp, rules, slot_off, nslots, out, k255, aligned);
     return hipGetLastError();
 }
 

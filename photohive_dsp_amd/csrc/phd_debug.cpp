@@ -142,6 +142,24 @@ extern "C" int phd_debug_k1_pixels(const uint8_t* rgb, long n, const phd_config*
     return 0;
 }
 
+// Which palette kernels a full-resolution report of this configuration runs,
+// from the functions run_reports itself asks (no device; tests/palette_grids.py).
+extern "C" int phd_debug_palette_path(const phd_config* cfg, int max_slots) {
+    clear_error();
+    std::string why;
+    if (!cfg || !validate_config(*cfg, &why)) {
+        set_error(cfg ? why : "phd_debug_palette_path: no configuration");
+        return -1;
+    }
+    const GridParams gp = make_grid(*cfg);
+    FastCls fc;
+    std::unique_ptr<ClassTables> t(new ClassTables());
+    make_class_tables(gp, &fc, t.get());
+    const bool fused = fused_palette_ok(gp);
+    return (fused ? 1 : 0) | (fc.k1t_cshift >= 0 ? 2 : 0) | (fc.k1t_cshift2 >= 0 ? 4 : 0) | (fc.use_thr ? 8 : 0) |
+           (t->codes_ok ? 16 : 0) | (palette_tail_batched(gp, 1, fused, max_slots) ? 32 : 0);
+}
+
 // One untimed full report of a device image: sets up the pipeline's buffers for
 // its size and leaves K1's channel sums at the start of the workspace.
 static bool report_once(Context* c, const uint8_t* d_rgb, int height, int width, const phd_config& cfg) {

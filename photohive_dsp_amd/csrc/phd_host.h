@@ -472,6 +472,10 @@ int run_device_batch(Context* c, const std::vector<BatchImage>& imgs, const std:
 // of a batch large enough for two lanes cut in two (views, typed and YUV calls)
 std::vector<std::vector<int>> mixed_groups(const std::vector<BatchImage>& imgs);
 void split_for_lanes(std::vector<std::vector<int>>* groups, void* stream);
+// The palette's second pass runs as one Kcut and one K3 launch over the batch
+// (else a pair of launches per image): full-resolution images whose palette is
+// fused, or whose batched K3 holds max_slots slots in LDS.
+bool palette_tail_batched(const GridParams& gp, int ds, bool fused, int max_slots);
 // Palette intermediates only (for parity tests).
 bool run_palette_trace(Context* c, const uint8_t* d_img, int height, int width, const phd_config& cfg,
                        std::vector<unsigned>* hist, PaletteDecision* dec,

@@ -265,6 +265,10 @@ bool fused_slot_sums(const GridParams& gp, const PaletteDecision& dec, const uns
     return true;
 }
 
+bool palette_tail_batched(const GridParams& gp, int ds, bool fused, int max_slots) {
+    return ds <= 1 && (fused || palette_sums_b_lds(gp.tl, max_slots) <= 160 * 1024);
+}
+
 // The palette's second pass for n images on s2, their B records (and the Kcut
 // list behind them) filled in the pinned workspace: one upload, then one Kcut
 // and one K3 launch over the whole batch, or (downsampled images, grids past
@@ -275,7 +279,7 @@ bool launch_palette_tail(Context* c, const Layout& L, int n, const uint8_t* cons
                          hipStream_t s2) {
     uint8_t* dw = (uint8_t*)c->d_ws;
     const uint8_t* hb = (const uint8_t*)c->h_pin + L.B(n, 0);
-    const bool batched = ds <= 1 && (fused || palette_sums_b_lds(gp.tl, max_slots) <= 160 * 1024);
+    const bool batched = palette_tail_batched(gp, ds, fused, max_slots);
     // the B records (and, batched, the Kcut list right after them): one copy
     PHD_HIP(hipMemcpyAsync(dw + L.B(n, 0), hb, (size_t)n * L.b_bytes + (batched ? L.e_bytes : 0),
                            hipMemcpyHostToDevice, s2));

@@ -179,7 +179,9 @@ for _name, _res, _args in (("phd_shutdown", None, []),
                              P(P(Full_Report_Data)), P(ctypes.c_int), ctypes.c_void_p]),
                            ("phd_convert_yuv_device", ctypes.c_int,
                             [P(PhdYuvView), ctypes.c_int, P(ctypes.c_void_p), ctypes.c_void_p]),
-                           ("phd_debug_yuv_view_host", ctypes.c_int, [P(PhdYuvView), ctypes.c_void_p])):
+                           ("phd_debug_yuv_view_host", ctypes.c_int, [P(PhdYuvView), ctypes.c_void_p]),
+                           # which palette kernels a configuration takes (host only)
+                           ("phd_debug_palette_path", ctypes.c_int, [P(PhdConfig), ctypes.c_int])):
     try:
         _f = getattr(lib, _name)
     except AttributeError:

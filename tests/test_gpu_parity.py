@@ -428,6 +428,11 @@ def test_config5_large_sizes_against_oracle(shape, kind):
                          ids=["default", "36_4_5", "thresholds"])
 def test_hsv_group_exhaustive_rgb_cube(cfg):
     """Device rgb2hsv + arm_octree group id == the C oracle for all 2^24 RGB8 triples."""
+    check_hsv_groups_rgb_cube(cfg)
+
+
+def check_hsv_groups_rgb_cube(cfg):
+    """(also run by tests/test_gpu_palette_grids.py on the grids past s_partitions = 6)"""
     phd, L, torch = _phd()
     from oracle import oracle as orc
     from photohive_dsp_amd.core import make_config

@@ -9,10 +9,14 @@ import ctypes
 import numpy as np
 import pytest
 
+from tests import palette_grids as pg
+
 CFGS = [{}, {"h_partitions": 36, "s_partitions": 4, "v_partitions": 5},
         {"black_thresh": 0.25, "gray_thresh": 0.2, "h_partitions": 12},
         {"h_partitions": 5, "s_partitions": 3, "v_partitions": 2},
-        {"h_partitions": 360, "s_partitions": 2, "v_partitions": 2}]
+        {"h_partitions": 360, "s_partitions": 2, "v_partitions": 2},
+        # a code table of 8 * 3 colour codes: more saturation classes than the threshold form holds
+        pg.grid("s8_table")]
 
 
 @pytest.fixture(scope="module")
@@ -29,6 +33,9 @@ def test_k1_pixel_classification_rgb_cube(cube, cfg):
     n = cube.shape[0]
     want_gid, want_hsv = orc.group_ids(cube, with_hsv=True, **cfg)
     c = make_config(**cfg)
+    if c.s_partitions > 6:
+        # the table K1 runs this grid, with Si from the full table (tests/test_palette_paths.py)
+        assert pg.path(cfg) & (pg.TABLE | pg.THR) == pg.TABLE, pg.describe(pg.path(cfg))
     cell = np.empty(n, np.int32)
     h = np.empty(n)
     s = np.empty(n)
