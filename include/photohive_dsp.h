@@ -448,6 +448,48 @@ int phd_convert_yuv_device(const phd_yuv_view* views, int n_images, uint8_t* con
  * memory into dst[3*height*width].  0, or -1 with phd_last_error. */
 int phd_debug_yuv_view_host(const phd_yuv_view* view, uint8_t* dst);
 
+/* ---- palette label maps ----------------------------------------------------------
+ * The reference's colour quantisation ends with every pixel in the list of one
+ * palette parent, or in none: group_irregular_pixels
+ * (src/color_quantization.c:342-479) moves the irregular groups' pixels into
+ * valid_parents[i]'s lists and calculate_avg_hsv (:510-576) averages each list
+ * into color_palette->averages[i]; the lists are then freed.  A label map is
+ * that assignment kept: for an H x W image reported at downsample_rate r it is
+ * mh x mw uint16, row-major, (mh, mw) = (H, W) for r <= 1, else (H / r, W / r)
+ * (downsample_rgb, src/image_processing.c:344-366); element k belongs to pixel
+ * k of the image rgb2hsv sees (src/interface.c:46), the downsampled image with
+ * its row-stride quirk.  label[k] = i when pixel k is in valid_parents[i]'s
+ * list, PHD_LABEL_NONE when it is in none (a tie's overflow).  Per slot,
+ * percentages[i] == (double)count(label == i) * (1.0 / (double)(mh*mw)), bit
+ * for bit. */
+enum { PHD_LABEL_NONE = 0xFFFF };
+
+/* phd_report_batch_device_mixed_crops plus label maps (the lists of
+ * src/color_quantization.c:342-479 that :510-576 averages).  d_labels: n_images
+ * device pointers; d_labels[i] receives (height/ds)*(width/ds) uint16 labels of
+ * image i (2-byte aligned), NULL = no map for that image; d_labels == NULL is
+ * exactly the call without maps.  Reports, statuses and return value as that
+ * call; the maps are complete when it returns.  An image that fails (size
+ * check, boxes, decision) leaves its buffer untouched or unspecified, never
+ * written outside its mh*mw elements. */
+int phd_report_batch_device_mixed_labels(const uint8_t* const* d_images, const int* heights,
+                                         const int* widths, int n_images, const phd_config* cfg,
+                                         const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
+                                         Full_Report_Data** out, int* status, void* stream);
+
+/* The quantised image of a label map (each pixel painted with the colour of
+ * the average calculate_avg_hsv, src/color_quantization.c:510-576, put it
+ * into): dst pixel k = the 3 bytes lut[3*label[k]..] or none_rgb for
+ * PHD_LABEL_NONE.  d_labels, d_dst: n_maps device pointers (3*mh*mw bytes per
+ * destination).  lut: HOST, 3*n_slots bytes (NULL allowed when n_slots is 0).
+ * A label >= n_slots that is not NONE fails nothing and is written as
+ * none_rgb.  Any map size from 1x1; at most 65535 maps.  One launch for all
+ * maps.  Enqueued on `stream`, or (NULL) on the library's stream and waited
+ * for.  0 or -1. */
+int phd_labels_to_rgb_device(const uint16_t* const* d_labels, const int* map_heights,
+                             const int* map_widths, int n_maps, const uint8_t* const* luts, const int* n_slots,
+                             const uint8_t none_rgb[3], uint8_t* const* d_dst, void* stream);
+
 /* Palette intermediates of one device-resident image, for bit-exact checks:
  * hist[TL] (arm_octree quantities), parents[*n_parents] (valid_parents in
  * palette order), kept[*n_parents] (pixels surviving group_irregular_pixels).
@@ -557,7 +599,8 @@ int phd_last_timings(double* ms, int n);
 /* Per-kernel GPU time from HIP events recorded on the launch stream around
  * every launch of the kernels in `mask` (bit k = kernel k: 0 hsv_stats,
  * 1 fft_rows, 2 fft_cols, 3 palette_cutoffs, 4 palette_sums, 5 sharpness,
- * 6 pack_views, 7 classify_views, 8 decode_views, 9 yuv_views).
+ * 6 pack_views, 7 classify_views, 8 decode_views, 9 yuv_views,
+ * 10 palette_labels).
  * phd_profile_kernels resets the counters; phd_profile_read returns the
  * accumulated milliseconds and launch count of one kernel. */
 int phd_profile_kernels(unsigned mask);

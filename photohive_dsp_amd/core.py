@@ -321,6 +321,83 @@ def reports_device_mixed(images, stream=None, salient_characters=None, **kw):
     return _run_reports(call, "reports_device_mixed", n, list(zip(hs, ws)), kw)
 
 
+def reports_device_labels(images, stream=None, salient_characters=None, **kw):
+    """reports_device_mixed plus each image's palette label map
+    (phd_report_batch_device_mixed_labels).  images: a list of uint8 [H, W, 3]
+    device tensors of any sizes, or one [N, H, W, 3] tensor.  Returns (reports,
+    labels): labels[i] is a torch.int16 [H // r, W // r] device tensor (r =
+    downsample_rate; [H, W] for r <= 1) with the bits of the C map: the palette
+    slot whose colour pixel k went into (an index into
+    Report.color_palette.colors), or -1 (PHD_LABEL_NONE) for a pixel no slot
+    kept."""
+    import torch
+    if isinstance(images, torch.Tensor):
+        if images.dim() != 4:
+            raise ValueError("expected a uint8 [N, H, W, 3] device tensor or a list of [H, W, 3] tensors")
+        images = list(images.unbind(0))
+    images = list(images)
+    for im in images:
+        if not isinstance(im, torch.Tensor) or im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 \
+                or not im.is_contiguous():
+            raise ValueError("expected contiguous uint8 [H, W, 3] device tensors")
+    n = len(images)
+    cfg = make_config(**kw)
+    crops = normalize_salient(salient_characters, n)
+    if n == 0:
+        return [], []
+    r = max(1, int(cfg.downsample_rate))
+    sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
+    labels = [torch.empty((h // r, w // r) if r > 1 else (h, w), dtype=torch.int16, device=im.device)
+              for im, (h, w) in zip(images, sizes)]
+    ptrs = (ctypes.c_void_p * n)(*[im.data_ptr() for im in images])
+    hs = (ctypes.c_int * n)(*[h for h, _ in sizes])
+    ws = (ctypes.c_int * n)(*[w for _, w in sizes])
+    maps = (ctypes.c_void_p * n)(*[m.data_ptr() for m in labels])
+    s = _stream_handle(stream)
+
+    def call(outs, st):
+        lib.phd_report_batch_device_mixed_labels(ptrs, hs, ws, n, ctypes.byref(cfg), crops[0] if crops else None,
+                                                 maps, outs, st, s)
+
+    return _run_reports(call, "reports_device_labels", n, sizes, kw), labels
+
+
+def quantize_device(labels, reports, none_rgb=(0, 0, 0), stream=None):
+    """The quantised images of label maps (phd_labels_to_rgb_device): per map a
+    uint8 [mh, mw, 3] device tensor whose pixel k is the palette colour of
+    labels[i][k] -- the integer triple Report.color_palette.colors[label], what
+    generate_color_palette_image draws -- or none_rgb where the label is -1.
+    labels: int16 [mh, mw] device tensors (reports_device_labels); reports: the
+    Report of each."""
+    import torch
+    labels, reports = list(labels), list(reports)
+    if len(labels) != len(reports):
+        raise ValueError(f"{len(labels)} label maps for {len(reports)} reports")
+    for m in labels:
+        if not isinstance(m, torch.Tensor) or m.dtype != torch.int16 or m.dim() != 2 or not m.is_contiguous() \
+                or m.numel() == 0:
+            raise ValueError("expected contiguous, non-empty int16 [mh, mw] device tensors")
+    none = [int(c) for c in none_rgb]
+    if len(none) != 3 or any(c < 0 or c > 255 for c in none):
+        raise ValueError("none_rgb must be three values in 0..255")
+    n = len(labels)
+    if n == 0:
+        return []
+    luts = [np.array([[int(c) for c in col] for col in rep.color_palette.colors], dtype=np.uint8).reshape(-1, 3)
+            for rep in reports]
+    out = [torch.empty((m.shape[0], m.shape[1], 3), dtype=torch.uint8, device=m.device) for m in labels]
+    maps = (ctypes.c_void_p * n)(*[m.data_ptr() for m in labels])
+    hs = (ctypes.c_int * n)(*[int(m.shape[0]) for m in labels])
+    ws = (ctypes.c_int * n)(*[int(m.shape[1]) for m in labels])
+    lut_ptrs = (ctypes.c_void_p * n)(*[(a.ctypes.data if a.size else None) for a in luts])
+    ns = (ctypes.c_int * n)(*[a.shape[0] for a in luts])
+    dst = (ctypes.c_void_p * n)(*[o.data_ptr() for o in out])
+    if lib.phd_labels_to_rgb_device(maps, hs, ws, n, lut_ptrs, ns, (ctypes.c_uint8 * 3)(*none), dst,
+                                    _stream_handle(stream)) != 0:
+        raise RuntimeError(f"quantize_device failed: {last_error()}")
+    return out
+
+
 def _report_views(entry, name, views, n, stream, salient_characters, kw):
     """reports_device_views, _typed and _yuv after their descriptors are made."""
     cfg = make_config(**kw)

@@ -13,33 +13,16 @@
 // (12 bytes, one dwordx3 load) per step so a wave reads 768 contiguous bytes.
 #include <cstdlib>
 
-#include "phd_device.h"
+#include "palette_tile.h"
 
 namespace phd {
 
 namespace {
 
-// LDS carve of K1 (one dynamic array, 16-B aligned base: no static __shared__).
+// (the LDS carve K1Lds, stage_tables and the group loads: palette_tile.h)
 constexpr int kK1Threads = 1024;             // Kcut block: 16 waves over one kChunk
 constexpr int kPalThreads = 512;             // K1 block: 8 waves, two resident per CU
 constexpr int kK3Threads = 1024;             // K3 block: one per CU (its LDS sums want the room)
-struct K1Lds {
-    static constexpr int k255 = 0;           // 256 doubles
-    static constexpr int ent = 2048;         // 256 ClsEnt (16 B)
-    static constexpr int red = 6144;         // 16 waves x 8 x u64
-    static constexpr int qn = 7168;          // Kcut scratch (16 B)
-    static constexpr int area = 7184;        // K1: 2 x (tl+1) x C chunk-count copies + tl; K3: rules, sums
-};
-static_assert(sizeof(ClsEnt) == 16, "ClsEnt is one 16-B LDS read");
-
-__device__ __forceinline__ void stage_tables(unsigned char* smem, const double* __restrict__ k255g,
-                                             const ClassTables* __restrict__ tabs) {
-    const int tid = threadIdx.x;
-    for (int i = tid; i < 256; i += blockDim.x) {
-        reinterpret_cast<double*>(smem + K1Lds::k255)[i] = k255g[i];
-        reinterpret_cast<ClsEnt*>(smem + K1Lds::ent)[i] = tabs->ent[i];
-    }
-}
 
 __device__ __forceinline__ void load4(const uint8_t* __restrict__ img, long p0, long end,
                                       bool aligned, unsigned (&k)[12], int& nvalid) {
@@ -69,9 +52,6 @@ __device__ __forceinline__ void load4(const uint8_t* __restrict__ img, long p0, 
     }
 }
 
-typedef const __attribute__((address_space(1))) unsigned gu32;   // global (not flat) loads
-
-__device__ __forceinline__ int px_byte(const unsigned (&w)[3], int b) { return (w[b >> 2] >> (8 * (b & 3))) & 255; }
 // One of four words by a runtime index, from values the compiler cannot trace
 // back to a register array (it would turn the selects into a dynamically
 // indexed array, i.e. scratch memory)
@@ -79,12 +59,6 @@ __device__ __forceinline__ unsigned sel4_opaque(int k, unsigned a, unsigned b, u
     asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
     return k == 0 ? a : (k == 1 ? b : (k == 2 ? c : d));
 }
-// pixel i (runtime, 0-3) of a 4-pixel group's words w0 w1 w2 in bits 0-23
-__device__ __forceinline__ unsigned px_word(unsigned w0, unsigned w1, unsigned w2, int i) {
-    const unsigned p1 = __builtin_amdgcn_alignbyte(w1, w0, 3u), p2 = __builtin_amdgcn_alignbyte(w2, w1, 2u);
-    return i == 0 ? w0 : (i == 1 ? p1 : (i == 2 ? p2 : w2 >> 8));
-}
-
 // Add one to lds[g] for every lane with g >= 0; a wave whose lanes all hit the
 // same group issues one atomic (flat regions of real images).
 __device__ __forceinline__ void hist_add(unsigned* lds, int g) {
@@ -132,8 +106,6 @@ __host__ __device__ __forceinline__ int k1_count_bytes(int tl, int cshift) {
     return (4 * (2 * (tl + 1) * (1 << cshift) + tl) + 15) & ~15;
 }
 
-typedef const __attribute__((address_space(1))) uint8_t gu8;
-
 // Byte b of pixel group st of w (registers; st is not a compile-time index).
 template <int kSteps>
 __device__ __forceinline__ int step_byte(const unsigned (&w)[kSteps][3], int st, int b) {
@@ -141,26 +113,6 @@ __device__ __forceinline__ int step_byte(const unsigned (&w)[kSteps][3], int st,
 #pragma unroll
     for (int k = 0; k < kSteps; k++) x = k == st ? w[k][b >> 2] : x;
     return (x >> (8 * (b & 3))) & 255;
-}
-
-// The 12 bytes of pixels p0..p0+3 of an image as three little-endian words.
-// Groups not wholly inside the image load from pixel 0 and are masked by the
-// caller (the `ok` bits); so every load is unconditional and stays in flight.
-template <bool kAligned>
-__device__ __forceinline__ void load_group(const uint8_t* ip, long p0, bool ok, unsigned (&w)[3]) {
-    const long a = ok ? 3 * p0 : 0;
-    if (kAligned) {
-        gu32* q = (gu32*)(ip + a);
-        w[0] = q[0];
-        w[1] = q[1];
-        w[2] = q[2];
-    } else {
-        gu8* b = (gu8*)(ip + a);
-#pragma unroll
-        for (int k = 0; k < 3; k++)
-            w[k] = (unsigned)b[4 * k] | (unsigned)b[4 * k + 1] << 8 | (unsigned)b[4 * k + 2] << 16 |
-                   (unsigned)b[4 * k + 3] << 24;
-    }
 }
 
 // K1 for downsample_rate == 1, over a whole batch of same-size images in one

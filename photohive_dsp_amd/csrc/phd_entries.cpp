@@ -505,13 +505,17 @@ void report_group(Context* cl, const std::vector<BatchImage>& imgs, const std::v
     if (m == 0) return;
     std::vector<const uint8_t*> rp(m);
     std::vector<const Crop_Boundaries*> cr(m);
+    std::vector<uint16_t*> lab(m);
+    bool maps = false;
     for (int q = 0; q < m; q++) {
         rp[q] = ptrs[ks[q]];
         cr[q] = imgs[grp[ks[q]]].boxes;
+        lab[q] = imgs[grp[ks[q]]].labels;
+        maps = maps || lab[q];
     }
     RunResults rr(m);
     run_reports(cl, rp.data(), m, imgs[grp[0]].height, imgs[grp[0]].width, cfg, nullptr, rr.o.data(), rr.st.data(),
-                (hipStream_t)stream, boxes ? cr.data() : nullptr);
+                (hipStream_t)stream, boxes ? cr.data() : nullptr, maps ? lab.data() : nullptr);
     for (int q = 0; q < m; q++) {
         r->o[ks[q]] = rr.o[q];
         r->st[ks[q]] = rr.st[q];
@@ -598,17 +602,23 @@ extern "C" int phd_report_batch_device_crops(const uint8_t* d_rgb, int n_images,
 // A single size group is not split across lanes.
 static int report_mixed(const char* entry, const uint8_t* const* d_images, const int* heights, const int* widths,
                         int n_images, const phd_config* cfg, const Crop_Boundaries* const* crops,
-                        Full_Report_Data** out, int* status, void* stream) {
+                        Full_Report_Data** out, int* status, void* stream, uint16_t* const* d_labels = nullptr) {
     clear_error();
     if (!d_images || !heights || !widths || !cfg || !out || !status || n_images <= 0) {
         set_error(std::string(entry) + ": bad arguments");
+        return -1;
+    }
+    // a label is a palette slot below PHD_LABEL_NONE's sign bit (int16 readers)
+    if (d_labels && make_grid(*cfg).tl >= 32768) {
+        set_error(std::string(entry) + ": label maps need fewer than 32768 octree groups (palette slots)");
         return -1;
     }
     Context* c = get_context();
     if (!c) return -1;
     std::vector<BatchImage> imgs;
     for (int i : valid_box_images(crops, heights, widths, 0, 0, n_images, out, status))
-        imgs.push_back({i, BatchImage::kPacked, d_images[i], heights[i], widths[i], crops ? crops[i] : nullptr});
+        imgs.push_back({i, BatchImage::kPacked, d_images[i], heights[i], widths[i], crops ? crops[i] : nullptr,
+                        d_labels ? d_labels[i] : nullptr});
     return run_device_batch(c, imgs, mixed_groups(imgs), run_packed_group, crops != nullptr, *cfg, out, status,
                             n_images, stream);
 }
@@ -626,6 +636,19 @@ extern "C" int phd_report_batch_device_mixed_crops(const uint8_t* const* d_image
                                                    int* status, void* stream) {
     return report_mixed(crops ? "phd_report_batch_device_mixed_crops" : "phd_report_batch_device_mixed", d_images,
                         heights, widths, n_images, cfg, crops, out, status, stream);
+}
+
+// phd_report_batch_device_mixed_crops plus each image's palette label map (the
+// parents' pixel lists after group_irregular_pixels,
+// src/color_quantization.c:342-479): the label launch follows the palette's
+// second pass of each run (ReportRun::label_maps).
+extern "C" int phd_report_batch_device_mixed_labels(const uint8_t* const* d_images, const int* heights,
+                                                    const int* widths, int n_images, const phd_config* cfg,
+                                                    const Crop_Boundaries* const* crops,
+                                                    uint16_t* const* d_labels, Full_Report_Data** out, int* status,
+                                                    void* stream) {
+    return report_mixed("phd_report_batch_device_mixed_labels", d_images, heights, widths, n_images, cfg, crops,
+                        out, status, stream, d_labels);
 }
 
 extern "C" int phd_report_batch_u8_crops(const uint8_t* const* images, const int* heights, const int* widths,

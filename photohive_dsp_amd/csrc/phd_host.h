@@ -133,10 +133,11 @@ bool gfft_run(const GfftPlan& p, const double2* in, double2* out, long count, do
 // ---- per-kernel event timing (opt-in, phd_profile_kernels) -----------------
 enum KernelId {
     kK1 = 0, kFftRows = 1, kFftCols = 2, kCutoffs = 3, kPalSums = 4, kSharp = 5, kPack = 6, kClassify = 7,
-    kDecode = 8, kYuv = 9, kNumKernels = 10
+    kDecode = 8, kYuv = 9, kLabels = 10, kNumKernels = 11
 };
 static_assert(kClassify == kProfClassify && kDecode == kProfDecode, "the decode launches' profiler slots");
 static_assert(kYuv == kProfYuv, "the YUV conversion launch's profiler slot");
+static_assert(kLabels == kProfLabels, "the label map launch's profiler slot");
 struct KernelProfiler {
     unsigned mask = 0;                              // kernels to bracket with events
     // mask bits 24-30: stride s > 1, only every s-th batch call is bracketed
@@ -234,7 +235,8 @@ struct Context {
     // the input stage (phd_inputs.cpp): the packed staging images of one run
     // of views, typed views or YUV views, the device table of the pack,
     // classify or conversion launch and its pinned copy; ev_views follows the
-    // last such launch (the table is rewritten only after it)
+    // last such launch (the table is rewritten only after it).  The label map
+    // launches' tables go through the same pair (upload_table)
     uint8_t* d_vstage = nullptr;
     size_t vstage_bytes = 0;
     void* d_views = nullptr;
@@ -416,9 +418,19 @@ Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int heigh
 // launches per box, sharpness.hip's k_sharp_pass).  img_crops (crops must be
 // NULL): image i's own boxes, NULL entries allowed, already validated
 // (crops_why); every box of the call goes through one batched launch.
+// labels (or NULL): image i's palette label map goes to labels[i] (device,
+// NULL entries allowed) on the tail stream after the palette's second pass;
+// complete when run_reports returns.
 bool run_reports(Context* c, const uint8_t* const* d_imgs, int n, int height, int width,
                  const phd_config& cfg, const Crop_Boundaries* crops, Full_Report_Data** out,
-                 int* status, hipStream_t stream, const Crop_Boundaries* const* img_crops = nullptr);
+                 int* status, hipStream_t stream, const Crop_Boundaries* const* img_crops = nullptr,
+                 uint16_t* const* labels = nullptr);
+// A launch table (phd_inputs.cpp): `bytes` go up on st into Context::d_views
+// through its pinned copy, the first `filled` from `host`, the rest zero, once
+// the last launch that read the table is done; table_launched: after the last
+// operation on st that reads it.
+bool upload_table(Context* c, const void* host, size_t filled, size_t bytes, hipStream_t st);
+bool table_launched(Context* c, hipStream_t st);
 // The batched sharpness stage of n same-size device images on st: uploads the
 // box table (one copy) and enqueues the two launches.  Box sums go to out0 +
 // img * out_stride + 2 * slot (doubles); out0 == nullptr: to a flat array in
@@ -439,6 +451,7 @@ struct BatchImage {
                                      // phd_typed_view or phd_yuv_view of it (staged on the lane)
     int height, width;
     const Crop_Boundaries* boxes;    // NULL: none
+    uint16_t* labels = nullptr;      // device: the image's label map, (height / ds) x (width / ds); NULL: none
 };
 // The reports and statuses of one run of m images, and their way back to the
 // caller's arrays: result k belongs to the caller's image idx[k].

@@ -12,12 +12,9 @@
 
 using namespace phd;
 
-namespace {
+namespace phd {
 
 // ---- launch tables ------------------------------------------------------------
-// (grid.y = view: at most this many views a launch)
-constexpr int kMaxViewsPerLaunch = 32768;
-
 // `bytes` of a launch table go up on st through the context's pinned copy
 // (d_views / h_views): the first `filled` bytes from `host`, the rest zero.
 // The table of the context's last launch is still read until that launch is
@@ -33,6 +30,19 @@ bool upload_table(Context* c, const void* host, size_t filled, size_t bytes, hip
     PHD_HIP(hipMemcpyAsync(c->d_views, c->h_views, bytes, hipMemcpyHostToDevice, st));
     return true;
 }
+
+// After the last operation on st that uses the table.
+bool table_launched(Context* c, hipStream_t st) {
+    PHD_HIP(hipEventRecord(c->ev_views, st));
+    return true;
+}
+
+}  // namespace phd
+
+namespace {
+
+// (grid.y = view: at most this many views a launch)
+constexpr int kMaxViewsPerLaunch = 32768;
 
 // The launches of a non-empty table of records on st, in chunks of
 // kMaxViewsPerLaunch: launch(device records, first record's number, count,
@@ -50,12 +60,6 @@ bool launch_views(Context* c, const std::vector<Rec>& recs, size_t extra, size_t
         const int m = (int)std::min<size_t>(kMaxViewsPerLaunch, recs.size() - k);
         PHD_HIP(launch((const Rec*)c->d_views + k, k, m, max_bands));
     }
-    return true;
-}
-
-// After the last operation on st that uses the table.
-bool table_launched(Context* c, hipStream_t st) {
-    PHD_HIP(hipEventRecord(c->ev_views, st));
     return true;
 }
 

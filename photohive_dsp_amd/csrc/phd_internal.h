@@ -249,6 +249,39 @@ hipError_t launch_palette_sums(const uint8_t* img, int height, int width, int ds
                                const GridParams& gp, const GroupRule* rules,
                                const double* slot_off, int nslots, double* out,
                                const double* k255, hipStream_t st);
+// ---- palette label maps (palette_labels.hip) --------------------------------
+// A label map is (height / ds) x (width / ds) uint16, row-major: per pixel of the
+// HSV image the palette slot whose list holds it after group_irregular_pixels
+// (src/color_quantization.c:342-479), or 0xFFFF (PHD_LABEL_NONE).
+constexpr int kProfLabels = 10;
+struct LabelDst {              // one destination of the batched launch (16 B)
+    uint16_t* map;
+    int img;                   // index into the run's image pointers and B records
+    int pad;
+};
+// The maps of n_dst images of a same-size batch (ds == 1) after the palette
+// tail, one launch: B records (rules at rules0) every b_stride bytes.  aligned:
+// every image with a destination is 4-byte aligned (word loads; else bytes).
+hipError_t launch_palette_labels_batch(const uint8_t* const* d_imgs, bool aligned, int height, int width,
+                                       const GridParams& gp, const FastCls& fc, const ClassTables* tabs,
+                                       const double* k255, const GroupRule* rules0, long b_stride,
+                                       const LabelDst* d_dst, int n_dst, hipStream_t st);
+// One image's map, any downsample rate (pixels gathered as launch_hsv_ds does).
+hipError_t launch_palette_labels(const uint8_t* img, int height, int width, int ds, const GridParams& gp,
+                                 const GroupRule* rules, const double* k255, uint16_t* map, hipStream_t st);
+// The quantised image of a label map: dst pixel k = lut[map[k]] (r | g << 8 |
+// b << 16 per slot, device) or none for labels >= n_slots.
+struct LabelRgbRec {
+    const uint16_t* map;
+    uint8_t* dst;
+    const unsigned* lut;
+    long npix;
+    int n_slots;
+    unsigned none;
+};
+// n <= 65535 maps in one launch (grid.y); max_npix: the largest map.
+hipError_t launch_labels_to_rgb(const LabelRgbRec* d_recs, int n, long max_npix, hipStream_t st);
+
 // Row pass: luma - avg of two rows as one complex sequence, FFT, split, write
 // the half spectra column-major into inter[wf][height].
 // Runtime-plan FFT passes over a batch of same-size images in one launch each

@@ -361,6 +361,7 @@ struct ReportArgs {
     int* status;
     hipStream_t stream;
     const Crop_Boundaries* const* img_crops;
+    uint16_t* const* labels;                                  // per-image label maps (device) or NULL
 };
 
 // How a call's FFT chain is launched: a row and a column launch per image, or
@@ -405,6 +406,7 @@ struct ReportRun : ReportArgs {
     uint8_t* hc() const { return hp + (size_t)n * L.a_bytes; }   // the C records on the host
 
     bool plan(), k1(), fft_chain(), palette_tail(), downloads(), assemble_groups(), timings();
+    bool label_maps();                                        // palette_tail()'s last step when labels != NULL
 };
 
 // Validation, tables, FFT selection, layout, buffers, the shared-box array.
@@ -685,7 +687,42 @@ bool ReportRun::palette_tail() {
     if (!launch_palette_tail(c, L, n, d_imgs, height, width, ds, gp, cls, nchunks, fused, dec.data(), ok.data(), n_ent,
                              max_slots, max_per_img, s2))
         return false;
+    if (labels && !label_maps()) return false;
     PHD_HIP(hipEventRecord(c->ev_tail, s2));
+    return true;
+}
+
+// The label maps of the images that asked for one and have a decision, on the
+// tail stream behind the palette's second pass (Kcut has filled the partial
+// groups' cutoff and last pixel in the B records): one launch over the run
+// where that pass is batched, else one launch per image.  ev_tail follows, so
+// the call's last download -- which the call waits for -- is behind the maps.
+bool ReportRun::label_maps() {
+    std::vector<LabelDst> dst;
+    bool aligned = true;
+    for (int i = 0; i < n; i++) {
+        if (!labels[i] || !ok[i]) continue;
+        dst.push_back(LabelDst{labels[i], i, 0});
+        aligned = aligned && (reinterpret_cast<uintptr_t>(d_imgs[i]) & 3) == 0;
+    }
+    if (dst.empty()) return true;
+    if (palette_tail_batched(gp, ds, fused, max_slots)) {
+        const size_t bytes = sizeof(LabelDst) * dst.size();
+        if (!upload_table(c, dst.data(), bytes, bytes, s2)) return false;
+        const int ps = c->prof.begin(kLabels, s2);
+        PHD_HIP(launch_palette_labels_batch((const uint8_t* const*)(dw + L.P_dev(n)), aligned, height, width, gp,
+                                            cls->fc, cls->d, c->d_k255,
+                                            (const GroupRule*)(dw + L.B(n, 0) + L.b_rules), (long)L.b_bytes,
+                                            (const LabelDst*)c->d_views, (int)dst.size(), s2));
+        c->prof.end(ps, s2);
+        return table_launched(c, s2);
+    }
+    for (const LabelDst& d : dst) {
+        const int ps = c->prof.begin(kLabels, s2);
+        PHD_HIP(launch_palette_labels(d_imgs[d.img], height, width, ds, gp,
+                                      (const GroupRule*)(dw + L.B(n, d.img) + L.b_rules), c->d_k255, d.map, s2));
+        c->prof.end(ps, s2);
+    }
     return true;
 }
 
@@ -813,8 +850,8 @@ bool ReportRun::timings() {
 
 bool run_reports(Context* c, const uint8_t* const* d_imgs, int n, int height, int width,
                  const phd_config& cfg, const Crop_Boundaries* crops, Full_Report_Data** out, int* status,
-                 hipStream_t stream, const Crop_Boundaries* const* img_crops) {
-    ReportRun r(ReportArgs{c, d_imgs, n, height, width, cfg, crops, out, status, stream, img_crops});
+                 hipStream_t stream, const Crop_Boundaries* const* img_crops, uint16_t* const* labels) {
+    ReportRun r(ReportArgs{c, d_imgs, n, height, width, cfg, crops, out, status, stream, img_crops, labels});
     return r.plan() && r.k1() && r.fft_chain() && r.palette_tail() && r.downloads() && r.assemble_groups() &&
            r.timings() && r.failures == 0;
 }

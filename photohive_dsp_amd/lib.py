@@ -114,6 +114,8 @@ PACK_VIEWS_KERNEL = 6      # the image views' gather (bit 6 of phd_profile_kerne
 CLASSIFY_VIEWS_KERNEL = 7  # the typed views' classifier (bit 7: "classify_views")
 DECODE_VIEWS_KERNEL = 8    # the typed views' decode to double planes (bit 8: "decode_views")
 YUV_VIEWS_KERNEL = 9       # the YCbCr views' conversion to RGB8 (bit 9: "yuv_views")
+PALETTE_LABELS_KERNEL = 10  # the palette label maps (bit 10: "palette_labels")
+LABEL_NONE = 0xFFFF        # PHD_LABEL_NONE: a pixel in no palette slot's list (-1 as int16)
 lib.phd_debug_time_kernel.restype = ctypes.c_int
 lib.phd_debug_time_kernel.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, P(PhdConfig),
                                       ctypes.c_int, ctypes.c_int, P(ctypes.c_double)]
@@ -180,6 +182,14 @@ for _name, _res, _args in (("phd_shutdown", None, []),
                            ("phd_convert_yuv_device", ctypes.c_int,
                             [P(PhdYuvView), ctypes.c_int, P(ctypes.c_void_p), ctypes.c_void_p]),
                            ("phd_debug_yuv_view_host", ctypes.c_int, [P(PhdYuvView), ctypes.c_void_p]),
+                           # palette label maps (labels: n device pointers to uint16 maps)
+                           ("phd_report_batch_device_mixed_labels", ctypes.c_int,
+                            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, P(PhdConfig),
+                             P(P(Crop_Boundaries)), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                             ctypes.c_void_p]),
+                           ("phd_labels_to_rgb_device", ctypes.c_int,
+                            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
                            # which palette kernels a configuration takes (host only)
                            ("phd_debug_palette_path", ctypes.c_int, [P(PhdConfig), ctypes.c_int])):
     try:
