@@ -477,6 +477,34 @@ int phd_report_batch_device_mixed_labels(const uint8_t* const* d_images, const i
                                          const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
                                          Full_Report_Data** out, int* status, void* stream);
 
+/* The same for device images as producers hold them:
+ * phd_report_batch_device_views, _typed_views and _yuv plus label maps, with the
+ * semantics of phd_report_batch_device_mixed_labels word for word (d_labels ==
+ * NULL is exactly the call without maps; d_labels[i] == NULL: no map for image
+ * i; complete on return; a failing image -- descriptor, size check, boxes,
+ * non-finite value, decision -- leaves its buffer untouched or unspecified and
+ * nothing is written outside its mh*mw elements; fewer than 32768 octree
+ * groups).  Map i is (height/ds) x (width/ds) in the view's (the luma's) own
+ * coordinates: element k belongs to pixel k of the image rgb2hsv sees
+ * (src/interface.c:46, src/image_processing.c:372-417) after the view has
+ * been gathered, converted or decoded.  An 8-bit image (a view, a YUV frame's
+ * RGB8 conversion, a typed view whose values are all j/255) gets the map of
+ * the same bytes through phd_report_batch_device_mixed_labels.  A typed view
+ * on the fp64 route gets the lists of src/color_quantization.c:342-479 for
+ * the doubles get_full_report_data (src/interface.c:20-94) would be given:
+ * the group of rgb2hsv + arm_octree (:108-161) on those doubles and the keep
+ * rule of group_irregular_pixels, with percentages[i] == (double)count(label
+ * == i) * (1.0 / (double)(mh*mw)) bit for bit as on the 8-bit route. */
+int phd_report_batch_device_views_labels(const phd_image_view* views, int n_images, const phd_config* cfg,
+                                         const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
+                                         Full_Report_Data** out, int* status, void* stream);
+int phd_report_batch_device_typed_views_labels(const phd_typed_view* views, int n_images, const phd_config* cfg,
+                                               const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
+                                               Full_Report_Data** out, int* status, void* stream);
+int phd_report_batch_device_yuv_labels(const phd_yuv_view* views, int n_images, const phd_config* cfg,
+                                       const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
+                                       Full_Report_Data** out, int* status, void* stream);
+
 /* The quantised image of a label map (each pixel painted with the colour of
  * the average calculate_avg_hsv, src/color_quantization.c:510-576, put it
  * into): dst pixel k = the 3 bytes lut[3*label[k]..] or none_rgb for

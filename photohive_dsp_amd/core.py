@@ -398,13 +398,41 @@ def quantize_device(labels, reports, none_rgb=(0, 0, 0), stream=None):
     return out
 
 
-def _report_views(entry, name, views, n, stream, salient_characters, kw):
-    """reports_device_views, _typed and _yuv after their descriptors are made."""
+def _report_views(entry, name, views, n, stream, salient_characters, kw, label_entry=None, devices=None):
+    """reports_device_views, _typed and _yuv after their descriptors are made.
+    label_entry (labels=True): the entry's _labels form; the maps are allocated
+    here as reports_device_labels allocates its own, image i's on devices[i],
+    and (reports, maps) is returned."""
     cfg = make_config(**kw)
     crops = normalize_salient(salient_characters, n)
+    if label_entry is not None and n == 0:
+        return [], []
     s = _stream_handle(stream)
-    return _run_reports(lambda outs, st: entry(views, n, ctypes.byref(cfg), crops[0] if crops else None, outs, st, s),
-                        name, n, _view_sizes(views, n), kw)
+    if label_entry is None:
+        return _run_reports(lambda outs, st: entry(views, n, ctypes.byref(cfg), crops[0] if crops else None, outs, st,
+                                                   s), name, n, _view_sizes(views, n), kw)
+    import torch
+    r = max(1, int(cfg.downsample_rate))
+    sizes = _view_sizes(views, n)
+    labels = [torch.empty((h // r, w // r) if r > 1 else (h, w), dtype=torch.int16, device=dev)
+              for (h, w), dev in zip(sizes, devices)]
+    maps = (ctypes.c_void_p * n)(*[m.data_ptr() for m in labels])
+    return _run_reports(lambda outs, st: label_entry(views, n, ctypes.byref(cfg), crops[0] if crops else None, maps,
+                                                     outs, st, s), name, n, sizes, kw), labels
+
+
+def _label_devices(keep, tensor_of):
+    """The device of each image's label map (labels=True): its tensor's.  A
+    descriptor that is no tensor names no device to allocate on."""
+    import torch
+    devs = []
+    for i, k in enumerate(keep):
+        t = tensor_of(k)
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"image {i}: labels=True needs torch tensors (the map is allocated on the image's "
+                             "device); call the C entry with maps of your own for descriptors")
+        devs.append(t.device)
+    return devs
 
 
 def _image_list(tensors, layout):
@@ -462,17 +490,23 @@ def make_views(tensors, layout="HWC", bgr=False):
     return views, tensors
 
 
-def reports_device_views(images, layout="HWC", bgr=False, stream=None, salient_characters=None, **kw):
+def reports_device_views(images, layout="HWC", bgr=False, stream=None, salient_characters=None, labels=False, **kw):
     """Reports for uint8 device tensors in any byte-strided layout (make_views:
     planar CHW, pitched rows, RGBA / BGRA, BGR, regions of interest, expanded
     grey planes; any sizes), without a repacked copy on the caller's side:
     views that are not packed RGB8 already are gathered into a library-owned
     staging image by one launch per run (phd_report_batch_device_views).
     salient_characters: per-image crop boxes in each view's own coordinates
-    (normalize_salient)."""
+    (normalize_salient).  labels=True: returns (reports, maps), maps[i] the
+    image's palette label map as reports_device_labels returns it (int16
+    [mh, mw] on the image's device, in the view's own coordinates;
+    phd_report_batch_device_views_labels); the images must be tensors."""
     views, keep = make_views(images, layout, bgr)
-    return _report_views(lib.phd_report_batch_device_views, "reports_device_views", views, len(keep), stream,
-                         salient_characters, kw)
+    if not labels:
+        return _report_views(lib.phd_report_batch_device_views, "reports_device_views", views, len(keep), stream,
+                             salient_characters, kw)
+    return _report_views(None, "reports_device_views", views, len(keep), stream, salient_characters, kw,
+                         lib.phd_report_batch_device_views_labels, _label_devices(keep, lambda t: t))
 
 
 def pack_views_device(images, layout="HWC", bgr=False, stream=None):
@@ -533,7 +567,7 @@ def make_typed_views(tensors, layout="HWC", bgr=False, max_value=None, snap_u8=F
 
 
 def reports_device_typed(images, layout="HWC", bgr=False, max_value=None, snap_u8=False, stream=None,
-                         salient_characters=None, **kw):
+                         salient_characters=None, labels=False, **kw):
     """Reports for device tensors of any element type in any byte-strided layout
     (make_typed_views; any sizes): a 16-bit decode, a float CHW tensor in 0..1,
     double planes already on the GPU.  Images whose values are exactly 8-bit
@@ -542,10 +576,16 @@ def reports_device_typed(images, layout="HWC", bgr=False, max_value=None, snap_u
     other image is decoded to doubles on the device and reported by the fp64
     pipeline of get_full_report_data on those doubles, with no host round trip
     of pixels (phd_report_batch_device_typed_views).  salient_characters:
-    per-image crop boxes in each view's own coordinates (normalize_salient)."""
+    per-image crop boxes in each view's own coordinates (normalize_salient).
+    labels=True: returns (reports, maps) as reports_device_views does
+    (phd_report_batch_device_typed_views_labels): an 8-bit image's map is that
+    of its bytes, an fp64-route image's the reference's lists on its doubles."""
     views, keep = make_typed_views(images, layout, bgr, max_value, snap_u8)
-    return _report_views(lib.phd_report_batch_device_typed_views, "reports_device_typed", views, len(keep), stream,
-                         salient_characters, kw)
+    if not labels:
+        return _report_views(lib.phd_report_batch_device_typed_views, "reports_device_typed", views, len(keep),
+                             stream, salient_characters, kw)
+    return _report_views(None, "reports_device_typed", views, len(keep), stream, salient_characters, kw,
+                         lib.phd_report_batch_device_typed_views_labels, _label_devices(keep, lambda t: t))
 
 
 def decode_views_device(images, layout="HWC", bgr=False, max_value=None, stream=None):
@@ -643,16 +683,23 @@ def make_yuv_views(frames, matrix="bt601", full_range=True, chroma="replicate", 
 
 
 def reports_device_yuv(frames, matrix="bt601", full_range=True, chroma="replicate", swap_uv=False, stream=None,
-                       salient_characters=None, **kw):
+                       salient_characters=None, labels=False, **kw):
     """Reports for 8-bit YCbCr frames on the current GPU (make_yuv_views: NV12
     surfaces, planar 4:2:0 / 4:2:2 / 4:4:4, YUY2 descriptors; any sizes): each
     frame is converted to RGB8 by the library's integer conversion
     (include/photohive_dsp.h), one launch per run, and reported as that image
     (phd_report_batch_device_yuv).  salient_characters: per-image crop boxes
-    in luma coordinates (normalize_salient)."""
+    in luma coordinates (normalize_salient).  labels=True: returns (reports,
+    maps), maps[i] the label map of frame i's RGB8 conversion in luma
+    coordinates, on the luma plane's device (phd_report_batch_device_yuv_labels;
+    the frames must be tensors)."""
     views, keep = make_yuv_views(frames, matrix, full_range, chroma, swap_uv)
-    return _report_views(lib.phd_report_batch_device_yuv, "reports_device_yuv", views, len(keep), stream,
-                         salient_characters, kw)
+    if not labels:
+        return _report_views(lib.phd_report_batch_device_yuv, "reports_device_yuv", views, len(keep), stream,
+                             salient_characters, kw)
+    return _report_views(None, "reports_device_yuv", views, len(keep), stream, salient_characters, kw,
+                         lib.phd_report_batch_device_yuv_labels,
+                         _label_devices(keep, lambda f: f[0] if isinstance(f, (tuple, list)) else f))
 
 
 def convert_yuv_device(frames, matrix="bt601", full_range=True, chroma="replicate", swap_uv=False, stream=None):

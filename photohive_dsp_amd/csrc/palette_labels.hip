@@ -17,26 +17,12 @@ namespace phd {
 namespace {
 
 constexpr int kLabThreads = 1024;            // 16 waves over one kChunk, as K3
-constexpr unsigned kNone = 0xFFFFu;          // PHD_LABEL_NONE
+constexpr unsigned kNone = kLabelNone;
 // waves/SIMD the batched kernel is sized for: two blocks per CU at <= 64 VGPRs
 // (the kThr forms spill 3 VGPRs), measured 46.4 / 42.0 us per 4000 x 3000
 // image against 52.9 / 45.2 at 4 (one block per CU, 70 VGPRs, no spill):
 // profiles/labels/labels_bench_*.log, DESIGN.md section 20
 constexpr int kLabMinWaves = 8;
-
-// {slot, cut, last, -} of a keep rule: a pixel of the group is kept when
-// slot >= 0 and its index < cut or == last (K3's packing).
-__device__ __forceinline__ uint4 pack_rule(const GroupRule& r) {
-    uint4 q;
-    q.x = (unsigned)r.slot;
-    q.y = r.partial ? r.cutoff : 0xFFFFFFFFu;
-    q.z = (r.partial && r.dangle) ? r.last : 0xFFFFFFFFu;
-    q.w = 0;
-    return q;
-}
-__device__ __forceinline__ unsigned label_of(const uint4& q, unsigned idx) {
-    return ((int)q.x >= 0 && (idx < q.y || idx == q.z)) ? (q.x & 0xFFFFu) : kNone;
-}
 
 // The label maps of a batch of same-size images (downsample_rate == 1) in one
 // launch.  Persistent blocks walk contiguous runs of (destination, chunk)

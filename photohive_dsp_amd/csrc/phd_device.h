@@ -317,6 +317,22 @@ __device__ __forceinline__ long src_pixel(long j, int width, int ds, int nw) {
     return y * (long)(ds - 1) * width + x * ds;
 }
 
+// A keep rule as the label kernels hold it in LDS (palette_labels.hip,
+// planar.hip): {slot, cut, last, -}, 16 B, one read per pixel.  A pixel of the
+// group is kept when slot >= 0 and its index < cut or == last (K3's packing).
+constexpr unsigned kLabelNone = 0xFFFFu;     // PHD_LABEL_NONE
+__device__ __forceinline__ uint4 pack_rule(const GroupRule& r) {
+    uint4 q;
+    q.x = (unsigned)r.slot;
+    q.y = r.partial ? r.cutoff : 0xFFFFFFFFu;
+    q.z = (r.partial && r.dangle) ? r.last : 0xFFFFFFFFu;
+    q.w = 0;
+    return q;
+}
+__device__ __forceinline__ unsigned label_of(const uint4& q, unsigned idx) {
+    return ((int)q.x >= 0 && (idx < q.y || idx == q.z)) ? (q.x & 0xFFFFu) : kLabelNone;
+}
+
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
 template <typename T>

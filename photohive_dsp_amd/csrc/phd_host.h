@@ -138,6 +138,7 @@ enum KernelId {
 static_assert(kClassify == kProfClassify && kDecode == kProfDecode, "the decode launches' profiler slots");
 static_assert(kYuv == kProfYuv, "the YUV conversion launch's profiler slot");
 static_assert(kLabels == kProfLabels, "the label map launch's profiler slot");
+static_assert(kPalSums == kProfPalSums, "the fp64 pipeline's k_planar_sums launch's profiler slot");
 struct KernelProfiler {
     unsigned mask = 0;                              // kernels to bracket with events
     // mask bits 24-30: stride s > 1, only every s-th batch call is bracketed
@@ -410,9 +411,10 @@ Full_Report_Data* report_planar(Context* c, const double* r, const double* g, co
 // report_planar after its upload: the fp64 planar pipeline on planes already
 // in c->d_planes (4 n doubles: P.r | P.g | P.b | luma) on the idle stream st;
 // cfg, the size and the boxes validated by the caller.  The typed entry runs
-// it on the planes k_decode_view filled.
+// it on the planes k_decode_view filled.  labels (or NULL): the image's palette
+// label map (device), complete when the call returns.
 Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int height, int width, const phd_config& cfg,
-                                       const Crop_Boundaries* crops, hipStream_t st);
+                                       const Crop_Boundaries* crops, hipStream_t st, uint16_t* labels);
 // Run the full report on n same-size device images.  out[i]/status[i] per image.
 // crops: one set of boxes for every image (the single-image entries; two
 // launches per box, sharpness.hip's k_sharp_pass).  img_crops (crops must be

@@ -266,7 +266,7 @@ void run_typed_group(Context* cl, const std::vector<BatchImage>& imgs, const std
         Full_Report_Data* o = nullptr;
         if (enqueue_decode_view(cl, tv(k), dp, st))
             o = report_planes_device(cl, PlanarSrc{dp, dp + n, dp + 2 * n}, height, width, cfg,
-                                     boxes ? imgs[grp[k]].boxes : nullptr, st);
+                                     boxes ? imgs[grp[k]].boxes : nullptr, st, imgs[grp[k]].labels);
         (void)hipStreamSynchronize(st);
         cl->prof.collect();
         if (o) {
@@ -282,14 +282,22 @@ void run_typed_group(Context* cl, const std::vector<BatchImage>& imgs, const std
 // src/interface.c:20-94, as GPU producers hold it): the mixed call over the
 // images whose descriptor (view_ok) and boxes are valid, a single size group
 // split as a same-size batch.  A bad view or bad boxes fail their image alone
-// (the last message stays).
+// (the last message stays).  d_labels (or NULL): image i's palette label map
+// goes to d_labels[i] (NULL entries allowed), as in
+// phd_report_batch_device_mixed_labels: an 8-bit image's from its run's label
+// launch (ReportRun::label_maps), an fp64 image's from k_planar_labels.
 template <class View, class Why>
 int report_views(const char* entry, BatchImage::Source kind, GroupFn run_group, const View* views, int n_images,
-                 const phd_config* cfg, const Crop_Boundaries* const* crops, Full_Report_Data** out, int* status,
-                 void* stream, Why view_ok) {
+                 const phd_config* cfg, const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
+                 Full_Report_Data** out, int* status, void* stream, Why view_ok) {
     clear_error();
     if (!views || !cfg || !out || !status || n_images <= 0) {
         set_error(std::string(entry) + ": bad arguments");
+        return -1;
+    }
+    // a label is a palette slot below PHD_LABEL_NONE's sign bit (int16 readers)
+    if (d_labels && make_grid(*cfg).tl >= 32768) {
+        set_error(std::string(entry) + ": label maps need fewer than 32768 octree groups (palette slots)");
         return -1;
     }
     std::vector<BatchImage> imgs;
@@ -299,7 +307,8 @@ int report_views(const char* entry, BatchImage::Source kind, GroupFn run_group, 
         status[i] = -1;
         std::string why;
         if (view_ok(views[i], &why) && (!crops || crops_why(crops[i], views[i].height, views[i].width, &why)))
-            imgs.push_back({i, kind, &views[i], views[i].height, views[i].width, crops ? crops[i] : nullptr});
+            imgs.push_back({i, kind, &views[i], views[i].height, views[i].width, crops ? crops[i] : nullptr,
+                            d_labels ? d_labels[i] : nullptr});
         else bad = "image " + std::to_string(i) + ": " + why;
     }
     Context* c = get_context();
@@ -347,12 +356,20 @@ int convert_views(const char* entry, const View* views, int n_images, Dst* const
 
 }  // namespace
 
-// Device images as byte-strided views, in the layouts GPU producers emit (pack_view.h).
+// Device images as byte-strided views, in the layouts GPU producers emit
+// (pack_view.h).  Each report entry below is its _labels entry with no maps.
+extern "C" int phd_report_batch_device_views_labels(const phd_image_view* views, int n_images, const phd_config* cfg,
+                                                    const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
+                                                    Full_Report_Data** out, int* status, void* stream) {
+    return report_views(d_labels ? "phd_report_batch_device_views_labels" : "phd_report_batch_device_views",
+                        BatchImage::kView, run_staged_group, views, n_images, cfg, crops, d_labels, out, status,
+                        stream, view_why);
+}
+
 extern "C" int phd_report_batch_device_views(const phd_image_view* views, int n_images, const phd_config* cfg,
                                              const Crop_Boundaries* const* crops, Full_Report_Data** out,
                                              int* status, void* stream) {
-    return report_views("phd_report_batch_device_views", BatchImage::kView, run_staged_group, views, n_images, cfg,
-                        crops, out, status, stream, view_why);
+    return phd_report_batch_device_views_labels(views, n_images, cfg, crops, nullptr, out, status, stream);
 }
 
 extern "C" int phd_pack_views_device(const phd_image_view* views, int n_images, uint8_t* const* d_dst, void* stream) {
@@ -361,11 +378,18 @@ extern "C" int phd_pack_views_device(const phd_image_view* views, int n_images, 
 }
 
 // Device YCbCr frames as decoders emit them (yuv_view.h).
+extern "C" int phd_report_batch_device_yuv_labels(const phd_yuv_view* views, int n_images, const phd_config* cfg,
+                                                  const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
+                                                  Full_Report_Data** out, int* status, void* stream) {
+    return report_views(d_labels ? "phd_report_batch_device_yuv_labels" : "phd_report_batch_device_yuv",
+                        BatchImage::kYuv, run_staged_group, views, n_images, cfg, crops, d_labels, out, status, stream,
+                        yuv_view_why);
+}
+
 extern "C" int phd_report_batch_device_yuv(const phd_yuv_view* views, int n_images, const phd_config* cfg,
                                            const Crop_Boundaries* const* crops, Full_Report_Data** out, int* status,
                                            void* stream) {
-    return report_views("phd_report_batch_device_yuv", BatchImage::kYuv, run_staged_group, views, n_images, cfg, crops,
-                        out, status, stream, yuv_view_why);
+    return phd_report_batch_device_yuv_labels(views, n_images, cfg, crops, nullptr, out, status, stream);
 }
 
 extern "C" int phd_convert_yuv_device(const phd_yuv_view* views, int n_images, uint8_t* const* d_dst, void* stream) {
@@ -374,11 +398,20 @@ extern "C" int phd_convert_yuv_device(const phd_yuv_view* views, int n_images, u
 }
 
 // Device images of any element type, as the reference's Pixels (src/types.h:5).
+extern "C" int phd_report_batch_device_typed_views_labels(const phd_typed_view* views, int n_images,
+                                                          const phd_config* cfg, const Crop_Boundaries* const* crops,
+                                                          uint16_t* const* d_labels, Full_Report_Data** out,
+                                                          int* status, void* stream) {
+    return report_views(d_labels ? "phd_report_batch_device_typed_views_labels"
+                                 : "phd_report_batch_device_typed_views",
+                        BatchImage::kTyped, run_typed_group, views, n_images, cfg, crops, d_labels, out, status,
+                        stream, typed_view_why);
+}
+
 extern "C" int phd_report_batch_device_typed_views(const phd_typed_view* views, int n_images, const phd_config* cfg,
                                                    const Crop_Boundaries* const* crops, Full_Report_Data** out,
                                                    int* status, void* stream) {
-    return report_views("phd_report_batch_device_typed_views", BatchImage::kTyped, run_typed_group, views, n_images,
-                        cfg, crops, out, status, stream, typed_view_why);
+    return phd_report_batch_device_typed_views_labels(views, n_images, cfg, crops, nullptr, out, status, stream);
 }
 
 // (one decode launch per image)

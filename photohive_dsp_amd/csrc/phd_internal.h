@@ -487,7 +487,14 @@ hipError_t launch_planar_k1(const PlanarSrc& P, int height, int width, int ds, c
                             unsigned short* chunk_hist, double* s_part, int* flags, hipStream_t st);
 hipError_t launch_planar_tail(const PlanarSrc& P, int height, int width, int ds, const GridParams& gp,
                               const unsigned short* chunk_hist, int nchunks, GroupRule* rules, const int* search,
-                              int n_search, const double* off, int nslots, double* out, hipStream_t st);
+                              int n_search, const double* off, int nslots, double* out, hipStream_t st,
+                              KernelProfiler* prof = nullptr);   // (k_planar_sums: profile slot 4)
+constexpr int kProfPalSums = 4;
+// The palette label map of the planes after launch_planar_tail (rules: its
+// device rules, cutoff / last filled): (height / ds) x (width / ds) uint16 at
+// map, per hsv pixel its group's slot when the keep rule keeps it, else 0xFFFF.
+hipError_t launch_planar_labels(const PlanarSrc& P, int height, int width, int ds, const GridParams& gp,
+                                const GroupRule* rules, uint16_t* map, hipStream_t st);
 
 // ---- global-memory batched FFTs and the generic 2-D path (fft_global.hip) ----
 // Blocks of the generic path's power / binning pass (= its max partials).

@@ -104,16 +104,22 @@ Full_Report_Data* report_planar(Context* c, const double* r, const double* g, co
         (void)hipStreamSynchronize(c->stream);
         return out;
     }
-    return report_planes_device(c, P, height, width, cfg, crops, st);
+    Full_Report_Data* out = report_planes_device(c, P, height, width, cfg, crops, st, nullptr);
+    (void)hipStreamSynchronize(st);
+    c->prof.collect();                                      // (k_planar_sums' events, when profiled)
+    return out;
 }
 
 // Everything after the upload: the fp64 planar pipeline on planes that are on
 // the device already -- P.r | P.g | P.b are the first 3 n doubles of
 // c->d_planes (4 n doubles), whose fourth plane takes the luma.  cfg, the size
 // and the boxes are validated; nothing but the planes' own producer is queued
-// on st (no buffer allocated here is in use).
+// on st (no buffer allocated here is in use).  labels (or NULL): the image's
+// palette label map (device, (height / ds) x (width / ds) uint16), written on
+// st behind the palette tail and complete when the call returns; untouched when
+// the image fails before its palette decision.
 Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int height, int width, const phd_config& cfg,
-                                       const Crop_Boundaries* crops, hipStream_t st) {
+                                       const Crop_Boundaries* crops, hipStream_t st, uint16_t* labels) {
     std::string why;
     const long n = (long)height * width;
     double* pgm = c->d_planes + 3 * n;
@@ -220,7 +226,13 @@ Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int heigh
                                 st));
     PHD_HIPN(launch_planar_tail(P, height, width, ds, gp, (const unsigned short*)(dr + R.chunk), nchunks,
                                 (GroupRule*)(dr + R.rules), (const int*)(dr + R.search), (int)dec.search.size(),
-                                (const double*)(dr + R.off), (int)dec.parents.size(), (double*)(dr + R.pal), st));
+                                (const double*)(dr + R.off), (int)dec.parents.size(), (double*)(dr + R.pal), st, &c->prof));
+    if (labels) {
+        // the parents' pixel lists (src/color_quantization.c:342-479): the tail has filled cutoff / last
+        const int ps = c->prof.begin(kLabels, st);
+        PHD_HIPN(launch_planar_labels(P, height, width, ds, gp, (const GroupRule*)(dr + R.rules), labels, st));
+        c->prof.end(ps, st);
+    }
     PHD_HIPN(hipMemcpyAsync(h.data() + R.part2, dr + R.part2, R.total - R.part2, hipMemcpyDeviceToHost, st));
     PHD_HIPN(hipStreamSynchronize(st));
     for (int ch = 0; ch < 3; ch++) {

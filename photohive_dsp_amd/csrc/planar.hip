@@ -17,7 +17,10 @@
 //     src/color_quantization.c:108-161) per pixel in fp64 (phd_device.h),
 //     the group histogram and its per-chunk counts, sum(s) for S-bar;
 //   * the tie-overflow cut-off search and calculate_avg_hsv's per-slot sums
-//     (src/color_quantization.c:414-450, 510-576) after the host decisions.
+//     (src/color_quantization.c:414-450, 510-576) after the host decisions;
+//   * the palette label map (the parents' pixel lists after
+//     group_irregular_pixels, src/color_quantization.c:342-479) from the same
+//     groups and keep rules (k_planar_labels).
 #include "phd_device.h"
 
 namespace phd {
@@ -142,10 +145,17 @@ __global__ __launch_bounds__(kPT) void k_planar_var(PlanarSrc P, long n, const d
     }
 }
 
+// rgb2hsv + arm_octree's group of one pixel's doubles: the one place the fp64
+// kernels get a group from (K1, the cut-off search, the sums, the label map).
+__device__ __forceinline__ int planar_group(double r, double g, double b, const GridParams& gp, double& h, double& s,
+                                            double& v) {
+    rgb2hsv(r, g, b, h, s, v);
+    return group_of(gp, h, s, v);
+}
+
 __device__ __forceinline__ int planar_group(const PlanarSrc& P, long p, const GridParams& gp, double& h, double& s,
                                             double& v) {
-    rgb2hsv(P.r[p], P.g[p], P.b[p], h, s, v);
-    return group_of(gp, h, s, v);
+    return planar_group(P.r[p], P.g[p], P.b[p], gp, h, s, v);
 }
 
 // K1 on doubles: one block per chunk of kChunk hsv pixels (downsample_rgb's
@@ -338,6 +348,101 @@ __global__ __launch_bounds__(kPT) void k_planar_sums(PlanarSrc P, long npix, int
     }
 }
 
+// ---- the label map on doubles ---------------------------------------------------
+// Threads and minimum waves per SIMD of k_planar_labels, chosen by measurement
+// on one 3000 x 4000 image (profiles/labels_inputs/kernel_*.log, DESIGN.md
+// section 21): 256 / 8 53.7 us, 256 / 4 54.4, 512 / 8 54.7, 1024 / 4 56.8,
+// 1024 / 8 57.3; at most 51 VGPRs and no scratch.  Overridable for A/B
+// builds: make variant V=... VFLAGS="-DPHD_PLAB_T=... -DPHD_PLAB_W=..."
+#ifndef PHD_PLAB_T
+#define PHD_PLAB_T 256
+#endif
+#ifndef PHD_PLAB_W
+#define PHD_PLAB_W 8
+#endif
+constexpr int kPlabThreads = PHD_PLAB_T, kPlabMinWaves = PHD_PLAB_W;
+
+// Four consecutive doubles of a plane from element j (j % 4 == 0): two 16-byte
+// loads when the plane's base is 16-byte aligned (the planes are 3 n contiguous
+// doubles, so for odd n every other plane is not), else element by element.
+__device__ __forceinline__ void load4(const double* __restrict__ p, long j, bool a16, double* x) {
+    if (a16) {
+        const double2 lo = *reinterpret_cast<const double2*>(p + j), hi = *reinterpret_cast<const double2*>(p + j + 2);
+        x[0] = lo.x;
+        x[1] = lo.y;
+        x[2] = hi.x;
+        x[3] = hi.y;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; i++) x[i] = p[j + i];
+    }
+}
+
+__device__ __forceinline__ unsigned planar_label(double r, double g, double b, const GridParams& gp,
+                                                 const uint4* rec, unsigned idx) {
+    double h, s, v;
+    const int grp = planar_group(r, g, b, gp, h, s, v);
+    // (a group outside the octree cannot pass the flags check: rec[tl] keeps nothing)
+    return label_of(rec[(unsigned)grp < (unsigned)gp.tl ? grp : gp.tl], idx);
+}
+
+// The palette label map of the fp64 pipeline (palette_labels.hip's rule on the
+// group planar_group gives, as K1 and k_planar_sums take it): one streaming
+// pass in the manner of k_palette_labels_b.  The keep rules sit packed in LDS
+// ({slot, cut, last}, 16 B: one ds_read_b128 per pixel); persistent blocks
+// stride over groups of 4 consecutive hsv pixels, one group per thread and
+// step; a group's labels leave as one 8-byte store when the map's base is
+// 8-byte aligned (4 pixels = 8 bytes: the base decides for the whole map),
+// else as four u16 stores.  The < 4 pixels of a partial final group: one lane.
+// kDs: downsample_rate > 1, the pixels gathered through src_pixel.
+template <bool kDs>
+__global__ __launch_bounds__(kPlabThreads, kPlabMinWaves) void k_planar_labels(
+        PlanarSrc P, long npix, int width, int ds, int nw, GridParams gp, const GroupRule* __restrict__ rules,
+        uint16_t* __restrict__ lab) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint4* rec = reinterpret_cast<uint4*>(smem);                          // [tl + 1]
+    const int tid = threadIdx.x, tl = gp.tl;
+    for (int i = tid; i < tl; i += kPlabThreads) rec[i] = pack_rule(rules[i]);
+    if (tid == 0) rec[tl] = make_uint4(0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u);
+    __syncthreads();
+    const bool wide = (reinterpret_cast<uintptr_t>(lab) & 7) == 0;
+    const bool ar = (reinterpret_cast<uintptr_t>(P.r) & 15) == 0, ag = (reinterpret_cast<uintptr_t>(P.g) & 15) == 0,
+               ab = (reinterpret_cast<uintptr_t>(P.b) & 15) == 0;
+    const long ngroups = npix >> 2;
+    for (long gi = (long)blockIdx.x * kPlabThreads + tid; gi < ngroups; gi += (long)gridDim.x * kPlabThreads) {
+        const long j0 = 4 * gi;
+        double r[4], g[4], b[4];
+        if constexpr (kDs) {
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const long p = src_pixel(j0 + i, width, ds, nw);
+                r[i] = P.r[p];
+                g[i] = P.g[p];
+                b[i] = P.b[p];
+            }
+        } else {
+            load4(P.r, j0, ar, r);
+            load4(P.g, j0, ag, g);
+            load4(P.b, j0, ab, b);
+        }
+        unsigned l[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) l[i] = planar_label(r[i], g[i], b[i], gp, rec, (unsigned)(j0 + i));
+        if (wide) {
+            *reinterpret_cast<uint2*>(lab + j0) = make_uint2(l[0] | l[1] << 16, l[2] | l[3] << 16);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; i++) lab[j0 + i] = (uint16_t)l[i];
+        }
+    }
+    if (blockIdx.x == 0 && tid == 0) {
+        for (long j = 4 * ngroups; j < npix; j++) {
+            const long p = src_pixel(j, width, ds, nw);
+            lab[j] = (uint16_t)planar_label(P.r[p], P.g[p], P.b[p], gp, rec, (unsigned)j);
+        }
+    }
+}
+
 unsigned grid_for(long n) { return (unsigned)std::max<long>(1, std::min<long>(kPlanarBlocks, (n + kPT - 1) / kPT)); }
 
 }  // namespace
@@ -373,7 +478,8 @@ hipError_t launch_planar_k1(const PlanarSrc& P, int height, int width, int ds, c
 
 hipError_t launch_planar_tail(const PlanarSrc& P, int height, int width, int ds, const GridParams& gp,
                               const unsigned short* chunk_hist, int nchunks, GroupRule* rules, const int* search,
-                              int n_search, const double* off, int nslots, double* out, hipStream_t st) {
+                              int n_search, const double* off, int nslots, double* out, hipStream_t st,
+                              KernelProfiler* prof) {
     int nw = width;
     long npix = (long)height * width;
     if (ds > 1) {
@@ -389,9 +495,39 @@ hipError_t launch_planar_tail(const PlanarSrc& P, int height, int width, int ds,
                                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
                             true);
         (void)once;
+        const int ps = prof_begin_kernel(prof, kProfPalSums, st);
         phd_launch(k_planar_sums, dim3((unsigned)((npix + kChunk - 1) / kChunk)), dim3(kPT), lds, st, P, npix, width,
                    ds, nw, gp, (const GroupRule*)rules, off, nslots, out);
+        prof_end(prof, ps, st);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_planar_labels(const PlanarSrc& P, int height, int width, int ds, const GridParams& gp,
+                                const GroupRule* rules, uint16_t* map, hipStream_t st) {
+    int nw = width;
+    long npix = (long)height * width;
+    if (ds > 1) {
+        nw = width / ds;
+        npix = (long)(short)(height / ds) * (short)nw;
+    }
+    if (npix <= 0) return hipSuccess;
+    const size_t lds = sizeof(uint4) * ((size_t)gp.tl + 1);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    const void* kfn = ds > 1 ? (const void*)k_planar_labels<true> : (const void*)k_planar_labels<false>;
+    // persistent blocks: as many as are resident at once
+    (void)hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, kPlabThreads, lds) != hipSuccess || per_cu < 1)
+        per_cu = 1;
+    const long steps = ((npix >> 2) + kPlabThreads - 1) / kPlabThreads;
+    const unsigned grid = (unsigned)std::max<long>(1, std::min<long>(steps, (long)per_cu * num_cus()));
+    if (ds > 1)
+        phd_launch(k_planar_labels<true>, dim3(grid), dim3(kPlabThreads), lds, st, P, npix, width, ds, nw, gp, rules,
+                   map);
+    else
+        phd_launch(k_planar_labels<false>, dim3(grid), dim3(kPlabThreads), lds, st, P, npix, width, ds, nw, gp, rules,
+                   map);
     return hipGetLastError();
 }
 

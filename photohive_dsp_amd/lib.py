@@ -187,6 +187,16 @@ for _name, _res, _args in (("phd_shutdown", None, []),
                             [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, P(PhdConfig),
                              P(P(Crop_Boundaries)), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                              ctypes.c_void_p]),
+                           # ... of views, typed views and YUV frames (the entries above plus `labels`)
+                           ("phd_report_batch_device_views_labels", ctypes.c_int,
+                            [P(PhdImageView), ctypes.c_int, P(PhdConfig), P(P(Crop_Boundaries)), ctypes.c_void_p,
+                             P(P(Full_Report_Data)), P(ctypes.c_int), ctypes.c_void_p]),
+                           ("phd_report_batch_device_typed_views_labels", ctypes.c_int,
+                            [P(PhdTypedView), ctypes.c_int, P(PhdConfig), P(P(Crop_Boundaries)), ctypes.c_void_p,
+                             P(P(Full_Report_Data)), P(ctypes.c_int), ctypes.c_void_p]),
+                           ("phd_report_batch_device_yuv_labels", ctypes.c_int,
+                            [P(PhdYuvView), ctypes.c_int, P(PhdConfig), P(P(Crop_Boundaries)), ctypes.c_void_p,
+                             P(P(Full_Report_Data)), P(ctypes.c_int), ctypes.c_void_p]),
                            ("phd_labels_to_rgb_device", ctypes.c_int,
                             [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
