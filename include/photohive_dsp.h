@@ -518,6 +518,89 @@ int phd_labels_to_rgb_device(const uint16_t* const* d_labels, const int* map_hei
                              const int* map_widths, int n_maps, const uint8_t* const* luts, const int* n_slots,
                              const uint8_t none_rgb[3], uint8_t* const* d_dst, void* stream);
 
+/* ---- box palettes ------------------------------------------------------------------
+ * Which palette colours a crop box holds: the lists of group_irregular_pixels
+ * (src/color_quantization.c:342-479) that calculate_avg_hsv (:510-576)
+ * averages, counted inside a box instead of over the image.  The box palette
+ * of a label map is counts[n_boxes][n_slots + 1], uint32, row-major: column
+ * s < n_slots is the number of map elements inside the box whose label is s,
+ * column n_slots everything else (PHD_LABEL_NONE and any label >= n_slots,
+ * which phd_labels_to_rgb_device paints as none_rgb).  A box (top, bottom,
+ * left, right) covers rows top <= y < bottom and columns left <= x < right,
+ * crop_pgm's convention (src/image_processing.c:213-232), as the boxes of
+ * salient_characters do for sharpness (src/interface.c:73).  Overlapping boxes
+ * are counted independently; every row sums to its box's element count; for a
+ * box that is the whole map, (double)counts[b][s] * (1.0 / (double)(mh*mw)) ==
+ * percentages[s] bit for bit.  The counts are integers added with integer
+ * atomics: the same on every run. */
+typedef struct phd_box_palette {
+    int n_boxes;        /* boxes[i]->N; 0 when map i has no boxes (boxes[i] NULL, N == 0) */
+    int n_slots;        /* n_slots[i]: color_palette->N of the map's report */
+    uint32_t* counts;   /* n_boxes x (n_slots + 1), row-major, one malloc; NULL when n_boxes == 0 */
+} phd_box_palette;
+/* Frees counts and zeroes the structs; bp == NULL is a no-op. */
+void phd_free_box_palettes(phd_box_palette* bp, int n);
+
+/* The box palettes of n_maps label maps (the lists of src/color_quantization.c:
+ * 342-479 and :510-576; boxes as src/image_processing.c:213-232 cuts them, given
+ * as src/interface.c:73 gives them) from any of the four _labels entries:
+ * d_labels[i] (device, 2-byte aligned) is map_heights[i] x map_widths[i];
+ * boxes[i] in MAP coordinates (NULL or N == 0: n_boxes == 0).  A box is valid
+ * when 0 <= left <= right <= mw and 0 <= top <= bottom <= mh; an empty box is
+ * allowed and counts 0.  An inverted or out-of-range box, a NULL map,
+ * non-positive sizes or n_slots outside 0..4096 (validate_config's group cap)
+ * fail the call with -1 before any device work, phd_last_error naming the map
+ * and the box, and out is left zeroed.  Every box of every map goes through one
+ * launch, enqueued on `stream` or (NULL) on the library's stream, and is waited
+ * for in both cases: the result is on the host.  out: n_maps structs, filled
+ * (release with phd_free_box_palettes).  0 or -1. */
+int phd_box_palettes_device(const uint16_t* const* d_labels, const int* map_heights, const int* map_widths,
+                            int n_maps, const int* n_slots, const Crop_Boundaries* const* boxes,
+                            phd_box_palette* out, void* stream);
+
+/* The four _labels entries plus box palettes (the lists of
+ * src/color_quantization.c:342-479 and :510-576 inside the boxes of
+ * src/image_processing.c:213-232 that src/interface.c:73 hands to sharpness):
+ * box_palettes, n_images structs, receives image i's box palette for the same
+ * `crops` that feed its sharpnesses, validated by the same rule; boxes are in
+ * IMAGE coordinates.  At downsample_rate r > 1 the map is mh x mw = (H / r) x
+ * (W / r) and a box covers the map elements whose nominal position (y*r, x*r)
+ * lies inside it: rows ceil(top / r) .. min(ceil(bottom / r), mh), columns
+ * ceil(left / r) .. min(ceil(right / r), mw); a box that is empty after scaling
+ * gives a row of zeros.  box_palettes == NULL is exactly the _labels call.
+ * d_labels may be NULL or hold NULL entries: an image with boxes and a map of
+ * the caller's is counted from that map, one without from a scratch map of the
+ * library's, written by the same label launch; an image without boxes gets no
+ * scratch and no count work and {0, n_slots, NULL}.  An image that fails (bad
+ * boxes or anything else) fails alone as in the _labels call and gets {0, 0,
+ * NULL}.  The palettes are complete when the call returns (release with
+ * phd_free_box_palettes).  Reports, statuses and return value as the _labels
+ * call; results do not depend on lanes, batch or run. */
+int phd_report_batch_device_mixed_box_palettes(const uint8_t* const* d_images, const int* heights,
+                                               const int* widths, int n_images, const phd_config* cfg,
+                                               const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
+                                               phd_box_palette* box_palettes, Full_Report_Data** out, int* status,
+                                               void* stream);
+int phd_report_batch_device_views_box_palettes(const phd_image_view* views, int n_images, const phd_config* cfg,
+                                               const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
+                                               phd_box_palette* box_palettes, Full_Report_Data** out, int* status,
+                                               void* stream);
+int phd_report_batch_device_typed_views_box_palettes(const phd_typed_view* views, int n_images, const phd_config* cfg,
+                                                     const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
+                                                     phd_box_palette* box_palettes, Full_Report_Data** out,
+                                                     int* status, void* stream);
+int phd_report_batch_device_yuv_box_palettes(const phd_yuv_view* views, int n_images, const phd_config* cfg,
+                                             const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
+                                             phd_box_palette* box_palettes, Full_Report_Data** out, int* status,
+                                             void* stream);
+
+/* Validation hook, host only (no GPU): the counting kernel's own item plan and
+ * row code (box_tiles.h; the lists of src/color_quantization.c:342-479 inside
+ * the boxes of src/image_processing.c:213-232) over one map of host memory.
+ * counts: boxes->N x (n_slots + 1).  0, or -1 with phd_last_error. */
+int phd_debug_box_counts_host(const uint16_t* map, int mh, int mw, int n_slots,
+                              const Crop_Boundaries* boxes, uint32_t* counts);
+
 /* Palette intermediates of one device-resident image, for bit-exact checks:
  * hist[TL] (arm_octree quantities), parents[*n_parents] (valid_parents in
  * palette order), kept[*n_parents] (pixels surviving group_irregular_pixels).
@@ -628,7 +711,7 @@ int phd_last_timings(double* ms, int n);
  * every launch of the kernels in `mask` (bit k = kernel k: 0 hsv_stats,
  * 1 fft_rows, 2 fft_cols, 3 palette_cutoffs, 4 palette_sums, 5 sharpness,
  * 6 pack_views, 7 classify_views, 8 decode_views, 9 yuv_views,
- * 10 palette_labels).
+ * 10 palette_labels, 11 box_palettes).
  * phd_profile_kernels resets the counters; phd_profile_read returns the
  * accumulated milliseconds and launch count of one kernel. */
 int phd_profile_kernels(unsigned mask);

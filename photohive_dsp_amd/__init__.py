@@ -1,6 +1,6 @@
 """PhotoHive_DSP for MI355X: drop-in get_report / Report / set_bounding_boxes
 backed by hand-written HIP kernels (PhotoHive_DSP_lib/libreport_data.so)."""
-from .core import (Report, convert_yuv_device, decode_views_device, get_report, get_reports,  # noqa: F401
+from .core import (Report, box_palettes_device, convert_yuv_device, decode_views_device, get_report, get_reports,  # noqa: F401
                    make_typed_views, make_views, make_yuv_views, nv12_planes, pack_views_device, quantize_device,
                    report_device, reports_device_labels, reports_device_mixed, reports_device_typed,
                    reports_device_views, reports_device_yuv, set_bounding_boxes, sharpness_device)

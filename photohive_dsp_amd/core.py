@@ -20,8 +20,8 @@ import numpy as np
 from .lib import last_error, lib
 from .structures import (PHD_ELEM_F16, PHD_ELEM_F32, PHD_ELEM_F64, PHD_ELEM_U8, PHD_ELEM_U16, PHD_VIEW_SNAP_U8,
                          PHD_YUV_BT601, PHD_YUV_BT709, PHD_YUV_CHROMA_REPLICATE, PHD_YUV_CHROMA_TRIANGLE,
-                         PHD_YUV_FULL, PHD_YUV_LIMITED, Crop_Boundaries, Full_Report_Data, PhdConfig, PhdImageView,
-                         PhdTypedView, PhdYuvView, Pixel_HSV, RGB_Statistics)
+                         PHD_YUV_FULL, PHD_YUV_LIMITED, Crop_Boundaries, Full_Report_Data, PhdBoxPalette, PhdConfig,
+                         PhdImageView, PhdTypedView, PhdYuvView, Pixel_HSV, RGB_Statistics)
 from .utils import hsv_to_rgb, image_pgm_to_pillow, to_rgb8
 
 DEFAULTS = dict(h_partitions=18, s_partitions=2, v_partitions=3, black_thresh=0.1, gray_thresh=0.1,
@@ -321,7 +321,7 @@ def reports_device_mixed(images, stream=None, salient_characters=None, **kw):
     return _run_reports(call, "reports_device_mixed", n, list(zip(hs, ws)), kw)
 
 
-def reports_device_labels(images, stream=None, salient_characters=None, **kw):
+def reports_device_labels(images, stream=None, salient_characters=None, box_palettes=False, **kw):
     """reports_device_mixed plus each image's palette label map
     (phd_report_batch_device_mixed_labels).  images: a list of uint8 [H, W, 3]
     device tensors of any sizes, or one [N, H, W, 3] tensor.  Returns (reports,
@@ -329,7 +329,10 @@ def reports_device_labels(images, stream=None, salient_characters=None, **kw):
     downsample_rate; [H, W] for r <= 1) with the bits of the C map: the palette
     slot whose colour pixel k went into (an index into
     Report.color_palette.colors), or -1 (PHD_LABEL_NONE) for a pixel no slot
-    kept."""
+    kept.  box_palettes=True: returns (reports, labels, palettes), palettes[i]
+    the image's box palette for its salient_characters boxes (image
+    coordinates) as box_palettes_device returns it
+    (phd_report_batch_device_mixed_box_palettes)."""
     import torch
     if isinstance(images, torch.Tensor):
         if images.dim() != 4:
@@ -344,7 +347,7 @@ def reports_device_labels(images, stream=None, salient_characters=None, **kw):
     cfg = make_config(**kw)
     crops = normalize_salient(salient_characters, n)
     if n == 0:
-        return [], []
+        return ([], [], []) if box_palettes else ([], [])
     r = max(1, int(cfg.downsample_rate))
     sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
     labels = [torch.empty((h // r, w // r) if r > 1 else (h, w), dtype=torch.int16, device=im.device)
@@ -359,7 +362,17 @@ def reports_device_labels(images, stream=None, salient_characters=None, **kw):
         lib.phd_report_batch_device_mixed_labels(ptrs, hs, ws, n, ctypes.byref(cfg), crops[0] if crops else None,
                                                  maps, outs, st, s)
 
-    return _run_reports(call, "reports_device_labels", n, sizes, kw), labels
+    if not box_palettes:
+        return _run_reports(call, "reports_device_labels", n, sizes, kw), labels
+    bp = (PhdBoxPalette * n)()
+    try:
+        reps = _run_reports(lambda outs, st: lib.phd_report_batch_device_mixed_box_palettes(
+            ptrs, hs, ws, n, ctypes.byref(cfg), crops[0] if crops else None, maps, bp, outs, st, s),
+            "reports_device_labels", n, sizes, kw)
+    except RuntimeError:
+        lib.phd_free_box_palettes(bp, n)
+        raise
+    return reps, labels, _take_box_palettes(bp, n)
 
 
 def quantize_device(labels, reports, none_rgb=(0, 0, 0), stream=None):
@@ -398,27 +411,91 @@ def quantize_device(labels, reports, none_rgb=(0, 0, 0), stream=None):
     return out
 
 
-def _report_views(entry, name, views, n, stream, salient_characters, kw, label_entry=None, devices=None):
+def _take_box_palettes(bp, n):
+    """The numpy copies of n filled phd_box_palette structs (uint32 [n_boxes,
+    n_slots + 1] each); the C blocks are freed."""
+    try:
+        out = []
+        for i in range(n):
+            nb, ns = int(bp[i].n_boxes), int(bp[i].n_slots)
+            a = np.zeros((nb, ns + 1), dtype=np.uint32)
+            if nb:
+                ctypes.memmove(a.ctypes.data, bp[i].counts, a.nbytes)
+            out.append(a)
+        return out
+    finally:
+        lib.phd_free_box_palettes(bp, n)
+
+
+def box_palettes_device(labels, reports_or_n_slots, boxes, stream=None):
+    """The box palettes of label maps (phd_box_palettes_device): per map a
+    numpy.uint32 [n_boxes, n_slots + 1] array; row b, column s is the number of
+    map elements inside box b whose label is slot s, the last column those in no
+    slot (-1, and any label >= n_slots).  labels: int16 [mh, mw] device tensors
+    (reports_device_labels); reports_or_n_slots: the Report of each map, or its
+    number of palette slots; boxes: what normalize_salient accepts, in MAP
+    coordinates (rows top <= y < bottom, columns left <= x < right; None or an
+    empty list: no boxes, an array of shape (0, n_slots + 1))."""
+    import torch
+    labels, slots = list(labels), list(reports_or_n_slots)
+    if len(labels) != len(slots):
+        raise ValueError(f"{len(labels)} label maps for {len(slots)} reports")
+    for m in labels:
+        if not isinstance(m, torch.Tensor) or m.dtype != torch.int16 or m.dim() != 2 or not m.is_contiguous() \
+                or m.numel() == 0:
+            raise ValueError("expected contiguous, non-empty int16 [mh, mw] device tensors")
+    n = len(labels)
+    crops = normalize_salient(boxes if boxes is not None else [None] * n, n)
+    if n == 0:
+        return []
+    ns = (ctypes.c_int * n)(*[(int(s) if isinstance(s, (int, np.integer)) else len(s.color_palette.colors))
+                              for s in slots])
+    maps = (ctypes.c_void_p * n)(*[m.data_ptr() for m in labels])
+    hs = (ctypes.c_int * n)(*[int(m.shape[0]) for m in labels])
+    ws = (ctypes.c_int * n)(*[int(m.shape[1]) for m in labels])
+    bp = (PhdBoxPalette * n)()
+    if lib.phd_box_palettes_device(maps, hs, ws, n, ns, crops[0], bp, _stream_handle(stream)) != 0:
+        raise RuntimeError(f"box_palettes_device failed: {last_error()}")
+    return _take_box_palettes(bp, n)
+
+
+def _report_views(entry, name, views, n, stream, salient_characters, kw, label_entry=None, devices=None,
+                  box_entry=None):
     """reports_device_views, _typed and _yuv after their descriptors are made.
-    label_entry (labels=True): the entry's _labels form; the maps are allocated
-    here as reports_device_labels allocates its own, image i's on devices[i],
-    and (reports, maps) is returned."""
+    devices (labels=True): the maps are allocated here as reports_device_labels
+    allocates its own, image i's on devices[i], and filled by label_entry, the
+    entry's _labels form.  box_entry (box_palettes=True): its _box_palettes
+    form; the box palettes are appended to the result.  Returns the reports,
+    (reports, maps), (reports, palettes) or (reports, maps, palettes)."""
     cfg = make_config(**kw)
     crops = normalize_salient(salient_characters, n)
-    if label_entry is not None and n == 0:
-        return [], []
+    want_maps = devices is not None
+    if n == 0 and (want_maps or box_entry is not None):
+        return ([],) * (1 + want_maps + (box_entry is not None))
     s = _stream_handle(stream)
-    if label_entry is None:
+    if not want_maps and box_entry is None:
         return _run_reports(lambda outs, st: entry(views, n, ctypes.byref(cfg), crops[0] if crops else None, outs, st,
                                                    s), name, n, _view_sizes(views, n), kw)
-    import torch
-    r = max(1, int(cfg.downsample_rate))
     sizes = _view_sizes(views, n)
-    labels = [torch.empty((h // r, w // r) if r > 1 else (h, w), dtype=torch.int16, device=dev)
-              for (h, w), dev in zip(sizes, devices)]
-    maps = (ctypes.c_void_p * n)(*[m.data_ptr() for m in labels])
-    return _run_reports(lambda outs, st: label_entry(views, n, ctypes.byref(cfg), crops[0] if crops else None, maps,
-                                                     outs, st, s), name, n, sizes, kw), labels
+    labels, maps = None, None
+    if want_maps:
+        import torch
+        r = max(1, int(cfg.downsample_rate))
+        labels = [torch.empty((h // r, w // r) if r > 1 else (h, w), dtype=torch.int16, device=dev)
+                  for (h, w), dev in zip(sizes, devices)]
+        maps = (ctypes.c_void_p * n)(*[m.data_ptr() for m in labels])
+    if box_entry is None:
+        return _run_reports(lambda outs, st: label_entry(views, n, ctypes.byref(cfg), crops[0] if crops else None,
+                                                         maps, outs, st, s), name, n, sizes, kw), labels
+    bp = (PhdBoxPalette * n)()
+    try:
+        reps = _run_reports(lambda outs, st: box_entry(views, n, ctypes.byref(cfg), crops[0] if crops else None, maps,
+                                                       bp, outs, st, s), name, n, sizes, kw)
+    except RuntimeError:
+        lib.phd_free_box_palettes(bp, n)
+        raise
+    pals = _take_box_palettes(bp, n)
+    return (reps, labels, pals) if want_maps else (reps, pals)
 
 
 def _label_devices(keep, tensor_of):
@@ -490,7 +567,8 @@ def make_views(tensors, layout="HWC", bgr=False):
     return views, tensors
 
 
-def reports_device_views(images, layout="HWC", bgr=False, stream=None, salient_characters=None, labels=False, **kw):
+def reports_device_views(images, layout="HWC", bgr=False, stream=None, salient_characters=None, labels=False,
+                         box_palettes=False, **kw):
     """Reports for uint8 device tensors in any byte-strided layout (make_views:
     planar CHW, pitched rows, RGBA / BGRA, BGR, regions of interest, expanded
     grey planes; any sizes), without a repacked copy on the caller's side:
@@ -500,13 +578,21 @@ def reports_device_views(images, layout="HWC", bgr=False, stream=None, salient_c
     (normalize_salient).  labels=True: returns (reports, maps), maps[i] the
     image's palette label map as reports_device_labels returns it (int16
     [mh, mw] on the image's device, in the view's own coordinates;
-    phd_report_batch_device_views_labels); the images must be tensors."""
+    phd_report_batch_device_views_labels); the images must be tensors.
+    box_palettes=True (independent of labels; no map tensor is allocated for
+    it): the images' box palettes are appended to the result, (reports,
+    palettes) or (reports, maps, palettes) -- per image a numpy.uint32
+    [n_boxes, n_slots + 1] array as box_palettes_device returns it, for its
+    salient_characters boxes (image coordinates); shape (0, n_slots + 1) for an
+    image without boxes (phd_report_batch_device_views_box_palettes)."""
     views, keep = make_views(images, layout, bgr)
-    if not labels:
+    if not labels and not box_palettes:
         return _report_views(lib.phd_report_batch_device_views, "reports_device_views", views, len(keep), stream,
                              salient_characters, kw)
     return _report_views(None, "reports_device_views", views, len(keep), stream, salient_characters, kw,
-                         lib.phd_report_batch_device_views_labels, _label_devices(keep, lambda t: t))
+                         lib.phd_report_batch_device_views_labels,
+                         _label_devices(keep, lambda t: t) if labels else None,
+                         lib.phd_report_batch_device_views_box_palettes if box_palettes else None)
 
 
 def pack_views_device(images, layout="HWC", bgr=False, stream=None):
@@ -567,7 +653,7 @@ def make_typed_views(tensors, layout="HWC", bgr=False, max_value=None, snap_u8=F
 
 
 def reports_device_typed(images, layout="HWC", bgr=False, max_value=None, snap_u8=False, stream=None,
-                         salient_characters=None, labels=False, **kw):
+                         salient_characters=None, labels=False, box_palettes=False, **kw):
     """Reports for device tensors of any element type in any byte-strided layout
     (make_typed_views; any sizes): a 16-bit decode, a float CHW tensor in 0..1,
     double planes already on the GPU.  Images whose values are exactly 8-bit
@@ -579,13 +665,17 @@ def reports_device_typed(images, layout="HWC", bgr=False, max_value=None, snap_u
     per-image crop boxes in each view's own coordinates (normalize_salient).
     labels=True: returns (reports, maps) as reports_device_views does
     (phd_report_batch_device_typed_views_labels): an 8-bit image's map is that
-    of its bytes, an fp64-route image's the reference's lists on its doubles."""
+    of its bytes, an fp64-route image's the reference's lists on its doubles.
+    box_palettes=True: the box palettes are appended as reports_device_views
+    appends them (phd_report_batch_device_typed_views_box_palettes)."""
     views, keep = make_typed_views(images, layout, bgr, max_value, snap_u8)
-    if not labels:
+    if not labels and not box_palettes:
         return _report_views(lib.phd_report_batch_device_typed_views, "reports_device_typed", views, len(keep),
                              stream, salient_characters, kw)
     return _report_views(None, "reports_device_typed", views, len(keep), stream, salient_characters, kw,
-                         lib.phd_report_batch_device_typed_views_labels, _label_devices(keep, lambda t: t))
+                         lib.phd_report_batch_device_typed_views_labels,
+                         _label_devices(keep, lambda t: t) if labels else None,
+                         lib.phd_report_batch_device_typed_views_box_palettes if box_palettes else None)
 
 
 def decode_views_device(images, layout="HWC", bgr=False, max_value=None, stream=None):
@@ -683,7 +773,7 @@ def make_yuv_views(frames, matrix="bt601", full_range=True, chroma="replicate", 
 
 
 def reports_device_yuv(frames, matrix="bt601", full_range=True, chroma="replicate", swap_uv=False, stream=None,
-                       salient_characters=None, labels=False, **kw):
+                       salient_characters=None, labels=False, box_palettes=False, **kw):
     """Reports for 8-bit YCbCr frames on the current GPU (make_yuv_views: NV12
     surfaces, planar 4:2:0 / 4:2:2 / 4:4:4, YUY2 descriptors; any sizes): each
     frame is converted to RGB8 by the library's integer conversion
@@ -692,14 +782,17 @@ def reports_device_yuv(frames, matrix="bt601", full_range=True, chroma="replicat
     in luma coordinates (normalize_salient).  labels=True: returns (reports,
     maps), maps[i] the label map of frame i's RGB8 conversion in luma
     coordinates, on the luma plane's device (phd_report_batch_device_yuv_labels;
-    the frames must be tensors)."""
+    the frames must be tensors).  box_palettes=True: the box palettes are
+    appended as reports_device_views appends them
+    (phd_report_batch_device_yuv_box_palettes)."""
     views, keep = make_yuv_views(frames, matrix, full_range, chroma, swap_uv)
-    if not labels:
+    if not labels and not box_palettes:
         return _report_views(lib.phd_report_batch_device_yuv, "reports_device_yuv", views, len(keep), stream,
                              salient_characters, kw)
     return _report_views(None, "reports_device_yuv", views, len(keep), stream, salient_characters, kw,
                          lib.phd_report_batch_device_yuv_labels,
-                         _label_devices(keep, lambda f: f[0] if isinstance(f, (tuple, list)) else f))
+                         _label_devices(keep, lambda f: f[0] if isinstance(f, (tuple, list)) else f) if labels
+                         else None, lib.phd_report_batch_device_yuv_box_palettes if box_palettes else None)
 
 
 def convert_yuv_device(frames, matrix="bt601", full_range=True, chroma="replicate", swap_uv=False, stream=None):

@@ -578,6 +578,10 @@ void destroy_context(Context* c) {
     if (c->h_views) (void)hipHostFree(c->h_views);
     c->h_views = nullptr;
     ev_destroy(c->ev_views);
+    dfree(c->d_boxpal);
+    dfree(c->d_labscratch);
+    if (c->h_boxpal) (void)hipHostFree(c->h_boxpal);
+    c->h_boxpal = nullptr;
     for (auto& p : c->d_stage2) dfree(p);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     c->h_pin = nullptr;

@@ -506,16 +506,20 @@ void report_group(Context* cl, const std::vector<BatchImage>& imgs, const std::v
     std::vector<const uint8_t*> rp(m);
     std::vector<const Crop_Boundaries*> cr(m);
     std::vector<uint16_t*> lab(m);
-    bool maps = false;
+    std::vector<phd_box_palette*> bp(m);
+    bool maps = false, pals = false;
     for (int q = 0; q < m; q++) {
         rp[q] = ptrs[ks[q]];
         cr[q] = imgs[grp[ks[q]]].boxes;
         lab[q] = imgs[grp[ks[q]]].labels;
+        bp[q] = imgs[grp[ks[q]]].box_pal;
         maps = maps || lab[q];
+        pals = pals || bp[q];
     }
     RunResults rr(m);
     run_reports(cl, rp.data(), m, imgs[grp[0]].height, imgs[grp[0]].width, cfg, nullptr, rr.o.data(), rr.st.data(),
-                (hipStream_t)stream, boxes ? cr.data() : nullptr, maps ? lab.data() : nullptr);
+                (hipStream_t)stream, boxes ? cr.data() : nullptr, maps ? lab.data() : nullptr,
+                pals ? bp.data() : nullptr);
     for (int q = 0; q < m; q++) {
         r->o[ks[q]] = rr.o[q];
         r->st[ks[q]] = rr.st[q];
@@ -602,14 +606,17 @@ extern "C" int phd_report_batch_device_crops(const uint8_t* d_rgb, int n_images,
 // A single size group is not split across lanes.
 static int report_mixed(const char* entry, const uint8_t* const* d_images, const int* heights, const int* widths,
                         int n_images, const phd_config* cfg, const Crop_Boundaries* const* crops,
-                        Full_Report_Data** out, int* status, void* stream, uint16_t* const* d_labels = nullptr) {
+                        Full_Report_Data** out, int* status, void* stream, uint16_t* const* d_labels = nullptr,
+                        phd_box_palette* box_palettes = nullptr) {
     clear_error();
+    if (box_palettes && n_images > 0)
+        for (int i = 0; i < n_images; i++) box_palettes[i] = phd_box_palette{0, 0, nullptr};
     if (!d_images || !heights || !widths || !cfg || !out || !status || n_images <= 0) {
         set_error(std::string(entry) + ": bad arguments");
         return -1;
     }
     // a label is a palette slot below PHD_LABEL_NONE's sign bit (int16 readers)
-    if (d_labels && make_grid(*cfg).tl >= 32768) {
+    if ((d_labels || box_palettes) && make_grid(*cfg).tl >= 32768) {
         set_error(std::string(entry) + ": label maps need fewer than 32768 octree groups (palette slots)");
         return -1;
     }
@@ -618,7 +625,7 @@ static int report_mixed(const char* entry, const uint8_t* const* d_images, const
     std::vector<BatchImage> imgs;
     for (int i : valid_box_images(crops, heights, widths, 0, 0, n_images, out, status))
         imgs.push_back({i, BatchImage::kPacked, d_images[i], heights[i], widths[i], crops ? crops[i] : nullptr,
-                        d_labels ? d_labels[i] : nullptr});
+                        d_labels ? d_labels[i] : nullptr, box_palettes ? box_palettes + i : nullptr});
     return run_device_batch(c, imgs, mixed_groups(imgs), run_packed_group, crops != nullptr, *cfg, out, status,
                             n_images, stream);
 }
@@ -649,6 +656,19 @@ extern "C" int phd_report_batch_device_mixed_labels(const uint8_t* const* d_imag
                                                     void* stream) {
     return report_mixed("phd_report_batch_device_mixed_labels", d_images, heights, widths, n_images, cfg, crops,
                         out, status, stream, d_labels);
+}
+
+// ... plus each image's box palette: per crop box, the elements of every
+// palette slot (ReportRun::label_maps counts behind the label launch).
+// box_palettes == NULL: exactly the call above.
+extern "C" int phd_report_batch_device_mixed_box_palettes(const uint8_t* const* d_images, const int* heights,
+                                                          const int* widths, int n_images, const phd_config* cfg,
+                                                          const Crop_Boundaries* const* crops,
+                                                          uint16_t* const* d_labels, phd_box_palette* box_palettes,
+                                                          Full_Report_Data** out, int* status, void* stream) {
+    return report_mixed(box_palettes ? "phd_report_batch_device_mixed_box_palettes"
+                                     : "phd_report_batch_device_mixed_labels",
+                        d_images, heights, widths, n_images, cfg, crops, out, status, stream, d_labels, box_palettes);
 }
 
 extern "C" int phd_report_batch_u8_crops(const uint8_t* const* images, const int* heights, const int* widths,

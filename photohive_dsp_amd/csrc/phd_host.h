@@ -17,6 +17,7 @@
 #include "../../include/photohive_dsp.h"
 #include "phd_internal.h"
 #include "batch_plan.h"
+#include "box_tiles.h"
 #include "sharp_plan.h"
 #include "views_plan.h"
 #include "yuv_plan.h"
@@ -133,8 +134,9 @@ bool gfft_run(const GfftPlan& p, const double2* in, double2* out, long count, do
 // ---- per-kernel event timing (opt-in, phd_profile_kernels) -----------------
 enum KernelId {
     kK1 = 0, kFftRows = 1, kFftCols = 2, kCutoffs = 3, kPalSums = 4, kSharp = 5, kPack = 6, kClassify = 7,
-    kDecode = 8, kYuv = 9, kLabels = 10, kNumKernels = 11
+    kDecode = 8, kYuv = 9, kLabels = 10, kBoxPalettes = 11, kNumKernels = 12
 };
+static_assert(kBoxPalettes == kProfBoxPalettes, "the box palette launch's profiler slot");
 static_assert(kClassify == kProfClassify && kDecode == kProfDecode, "the decode launches' profiler slots");
 static_assert(kYuv == kProfYuv, "the YUV conversion launch's profiler slot");
 static_assert(kLabels == kProfLabels, "the label map launch's profiler slot");
@@ -245,6 +247,16 @@ struct Context {
     void* h_views = nullptr;
     size_t h_views_bytes = 0;
     hipEvent_t ev_views = nullptr;
+    // box palettes (phd_boxpal.cpp): the counters of a launch's boxes and
+    // their pinned copy
+    void* d_boxpal = nullptr;
+    size_t boxpal_bytes = 0;
+    void* h_boxpal = nullptr;
+    size_t h_boxpal_bytes = 0;
+    // the label maps of a run's images that have boxes to count and no map of
+    // the caller's: 2 * mh * mw bytes each at 256-byte steps, grow-only
+    void* d_labscratch = nullptr;
+    size_t labscratch_bytes = 0;
     // typed views: the snap tables' device copy (views_plan.h: snap_tables)
     uint8_t* d_snap = nullptr;
     hipEvent_t ev[8] = {};
@@ -412,9 +424,12 @@ Full_Report_Data* report_planar(Context* c, const double* r, const double* g, co
 // in c->d_planes (4 n doubles: P.r | P.g | P.b | luma) on the idle stream st;
 // cfg, the size and the boxes validated by the caller.  The typed entry runs
 // it on the planes k_decode_view filled.  labels (or NULL): the image's palette
-// label map (device), complete when the call returns.
+// label map (device), complete when the call returns.  box_pal (or NULL): the
+// image's box palette (zeroed by the caller), counted from labels or from a
+// map in Context::d_labscratch.
 Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int height, int width, const phd_config& cfg,
-                                       const Crop_Boundaries* crops, hipStream_t st, uint16_t* labels);
+                                       const Crop_Boundaries* crops, hipStream_t st, uint16_t* labels,
+                                       phd_box_palette* box_pal = nullptr);
 // Run the full report on n same-size device images.  out[i]/status[i] per image.
 // crops: one set of boxes for every image (the single-image entries; two
 // launches per box, sharpness.hip's k_sharp_pass).  img_crops (crops must be
@@ -423,10 +438,14 @@ Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int heigh
 // labels (or NULL): image i's palette label map goes to labels[i] (device,
 // NULL entries allowed) on the tail stream after the palette's second pass;
 // complete when run_reports returns.
+// box_pal (or NULL): image i's box palette goes to *box_pal[i] (NULL entries
+// allowed; zeroed by the caller): n_slots for every reported image, the counts
+// of its img_crops boxes where it has any -- from labels[i], or from a scratch
+// map of the context (Context::d_labscratch) where the caller gave none.
 bool run_reports(Context* c, const uint8_t* const* d_imgs, int n, int height, int width,
                  const phd_config& cfg, const Crop_Boundaries* crops, Full_Report_Data** out,
                  int* status, hipStream_t stream, const Crop_Boundaries* const* img_crops = nullptr,
-                 uint16_t* const* labels = nullptr);
+                 uint16_t* const* labels = nullptr, phd_box_palette* const* box_pal = nullptr);
 // A launch table (phd_inputs.cpp): `bytes` go up on st into Context::d_views
 // through its pinned copy, the first `filled` from `host`, the rest zero, once
 // the last launch that read the table is done; table_launched: after the last
@@ -439,6 +458,23 @@ bool table_launched(Context* c, hipStream_t st);
 // the context's own buffer (*flat_dev; plan slots must be flat).
 bool enqueue_sharpness(Context* c, const uint8_t* const* d_imgs, int n, int width, const SharpPlan& plan,
                        double* out0, long out_stride, hipStream_t st, double** flat_dev = nullptr);
+// The box palettes of a launch (phd_boxpal.cpp; plan and row code:
+// box_tiles.h): the boxes' records, box_plan's items and the counters they
+// fill, box b's n_slots + 1 at recs[b].out.
+struct BoxJob {
+    std::vector<BoxRec> recs;
+    std::vector<BoxItem> items;
+    long long counters = 0;
+    // a box of map coordinates (rows top <= y < bottom, columns left <= x < right)
+    void add(const uint16_t* map, int mw, int n_slots, int top, int bottom, int left, int right);
+    // the boxes of an image (image coordinates) on its mh x mw map of downsample_rate ds
+    void add_image(const uint16_t* map, int mh, int mw, int ds, int n_slots, const Crop_Boundaries* b);
+};
+bool box_palette_fill(phd_box_palette* bp, int n_boxes, int n_slots, const uint32_t* h);
+// The job on st: its table goes up (upload_table), Context::d_boxpal is zeroed
+// by one memset, one launch counts, one copy brings the counters to
+// Context::h_boxpal.  The caller waits for st before it reads them.
+bool enqueue_box_job(Context* c, const BoxJob& job, hipStream_t st);
 // A grow-only pinned block of at least `need` bytes (the old one is freed at once)
 bool grow_pinned(void** p, size_t* cap, size_t need);
 
@@ -454,6 +490,7 @@ struct BatchImage {
     int height, width;
     const Crop_Boundaries* boxes;    // NULL: none
     uint16_t* labels = nullptr;      // device: the image's label map, (height / ds) x (width / ds); NULL: none
+    phd_box_palette* box_pal = nullptr;   // the caller's struct for the image's box palette; NULL: none
 };
 // The reports and statuses of one run of m images, and their way back to the
 // caller's arrays: result k belongs to the caller's image idx[k].

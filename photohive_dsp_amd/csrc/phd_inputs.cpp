@@ -266,7 +266,8 @@ void run_typed_group(Context* cl, const std::vector<BatchImage>& imgs, const std
         Full_Report_Data* o = nullptr;
         if (enqueue_decode_view(cl, tv(k), dp, st))
             o = report_planes_device(cl, PlanarSrc{dp, dp + n, dp + 2 * n}, height, width, cfg,
-                                     boxes ? imgs[grp[k]].boxes : nullptr, st, imgs[grp[k]].labels);
+                                     boxes ? imgs[grp[k]].boxes : nullptr, st, imgs[grp[k]].labels,
+                                     imgs[grp[k]].box_pal);
         (void)hipStreamSynchronize(st);
         cl->prof.collect();
         if (o) {
@@ -289,14 +290,17 @@ void run_typed_group(Context* cl, const std::vector<BatchImage>& imgs, const std
 template <class View, class Why>
 int report_views(const char* entry, BatchImage::Source kind, GroupFn run_group, const View* views, int n_images,
                  const phd_config* cfg, const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
-                 Full_Report_Data** out, int* status, void* stream, Why view_ok) {
+                 Full_Report_Data** out, int* status, void* stream, Why view_ok,
+                 phd_box_palette* box_palettes = nullptr) {
     clear_error();
+    if (box_palettes && n_images > 0)
+        for (int i = 0; i < n_images; i++) box_palettes[i] = phd_box_palette{0, 0, nullptr};
     if (!views || !cfg || !out || !status || n_images <= 0) {
         set_error(std::string(entry) + ": bad arguments");
         return -1;
     }
     // a label is a palette slot below PHD_LABEL_NONE's sign bit (int16 readers)
-    if (d_labels && make_grid(*cfg).tl >= 32768) {
+    if ((d_labels || box_palettes) && make_grid(*cfg).tl >= 32768) {
         set_error(std::string(entry) + ": label maps need fewer than 32768 octree groups (palette slots)");
         return -1;
     }
@@ -308,7 +312,7 @@ int report_views(const char* entry, BatchImage::Source kind, GroupFn run_group, 
         std::string why;
         if (view_ok(views[i], &why) && (!crops || crops_why(crops[i], views[i].height, views[i].width, &why)))
             imgs.push_back({i, kind, &views[i], views[i].height, views[i].width, crops ? crops[i] : nullptr,
-                            d_labels ? d_labels[i] : nullptr});
+                            d_labels ? d_labels[i] : nullptr, box_palettes ? box_palettes + i : nullptr});
         else bad = "image " + std::to_string(i) + ": " + why;
     }
     Context* c = get_context();
@@ -412,6 +416,41 @@ extern "C" int phd_report_batch_device_typed_views(const phd_typed_view* views, 
                                                    const Crop_Boundaries* const* crops, Full_Report_Data** out,
                                                    int* status, void* stream) {
     return phd_report_batch_device_typed_views_labels(views, n_images, cfg, crops, nullptr, out, status, stream);
+}
+
+// The three _labels entries plus each image's box palette (per crop box, the
+// elements of every palette slot: ReportRun::label_maps, report_planes_device).
+// box_palettes == NULL: exactly the _labels entry.
+extern "C" int phd_report_batch_device_views_box_palettes(const phd_image_view* views, int n_images,
+                                                          const phd_config* cfg, const Crop_Boundaries* const* crops,
+                                                          uint16_t* const* d_labels, phd_box_palette* box_palettes,
+                                                          Full_Report_Data** out, int* status, void* stream) {
+    if (!box_palettes)
+        return phd_report_batch_device_views_labels(views, n_images, cfg, crops, d_labels, out, status, stream);
+    return report_views("phd_report_batch_device_views_box_palettes", BatchImage::kView, run_staged_group, views,
+                        n_images, cfg, crops, d_labels, out, status, stream, view_why, box_palettes);
+}
+
+extern "C" int phd_report_batch_device_yuv_box_palettes(const phd_yuv_view* views, int n_images, const phd_config* cfg,
+                                                        const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
+                                                        phd_box_palette* box_palettes, Full_Report_Data** out,
+                                                        int* status, void* stream) {
+    if (!box_palettes)
+        return phd_report_batch_device_yuv_labels(views, n_images, cfg, crops, d_labels, out, status, stream);
+    return report_views("phd_report_batch_device_yuv_box_palettes", BatchImage::kYuv, run_staged_group, views,
+                        n_images, cfg, crops, d_labels, out, status, stream, yuv_view_why, box_palettes);
+}
+
+extern "C" int phd_report_batch_device_typed_views_box_palettes(const phd_typed_view* views, int n_images,
+                                                                const phd_config* cfg,
+                                                                const Crop_Boundaries* const* crops,
+                                                                uint16_t* const* d_labels,
+                                                                phd_box_palette* box_palettes, Full_Report_Data** out,
+                                                                int* status, void* stream) {
+    if (!box_palettes)
+        return phd_report_batch_device_typed_views_labels(views, n_images, cfg, crops, d_labels, out, status, stream);
+    return report_views("phd_report_batch_device_typed_views_box_palettes", BatchImage::kTyped, run_typed_group, views,
+                        n_images, cfg, crops, d_labels, out, status, stream, typed_view_why, box_palettes);
 }
 
 // (one decode launch per image)

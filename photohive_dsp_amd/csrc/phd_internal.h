@@ -282,6 +282,15 @@ struct LabelRgbRec {
 // n <= 65535 maps in one launch (grid.y); max_npix: the largest map.
 hipError_t launch_labels_to_rgb(const LabelRgbRec* d_recs, int n, long max_npix, hipStream_t st);
 
+// ---- box palettes (box_palette.hip; plan and row code: box_tiles.h) ----------
+// Per crop box of a label map, the elements of every palette slot: nitems items
+// of box_plan over the boxes d_recs, added into d_counts (zeroed by the caller).
+constexpr int kProfBoxPalettes = 11;
+struct BoxRec;
+struct BoxItem;
+hipError_t launch_box_counts(const BoxRec* d_recs, const BoxItem* d_items, int nitems, unsigned* d_counts,
+                             hipStream_t st);
+
 // Row pass: luma - avg of two rows as one complex sequence, FFT, split, write
 // the half spectra column-major into inter[wf][height].
 // Runtime-plan FFT passes over a batch of same-size images in one launch each

@@ -119,7 +119,8 @@ Full_Report_Data* report_planar(Context* c, const double* r, const double* g, co
 // st behind the palette tail and complete when the call returns; untouched when
 // the image fails before its palette decision.
 Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int height, int width, const phd_config& cfg,
-                                       const Crop_Boundaries* crops, hipStream_t st, uint16_t* labels) {
+                                       const Crop_Boundaries* crops, hipStream_t st, uint16_t* labels,
+                                       phd_box_palette* box_pal) {
     std::string why;
     const long n = (long)height * width;
     double* pgm = c->d_planes + 3 * n;
@@ -140,6 +141,13 @@ Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int heigh
     if (!ensure_device(&c->d_prec, &c->prec_bytes, R.total) ||
         !ensure_device((void**)&c->d_inter, &c->inter_bytes, sizeof(double2) * ((size_t)height * wf + 1024)))
         return nullptr;
+    // box palettes: the boxes are counted from the caller's map, or from one in the context's scratch
+    const bool count_boxes = box_pal && ncrops > 0;
+    const int mh = ds > 1 ? height / ds : height, mw = ds > 1 ? width / ds : width;
+    if (count_boxes && !labels) {
+        if (!ensure_device(&c->d_labscratch, &c->labscratch_bytes, sizeof(uint16_t) * (size_t)mh * mw)) return nullptr;
+        labels = (uint16_t*)c->d_labscratch;
+    }
     uint8_t* dr = (uint8_t*)c->d_prec;
     int* flags = (int*)(dr + R.flags);
     PHD_HIPN(hipMemsetAsync(dr, 0, R.total, st));
@@ -233,6 +241,12 @@ Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int heigh
         PHD_HIPN(launch_planar_labels(P, height, width, ds, gp, (const GroupRule*)(dr + R.rules), labels, st));
         c->prof.end(ps, st);
     }
+    if (count_boxes) {
+        // the same counting kernel as the 8-bit runs', behind k_planar_labels on this stream
+        BoxJob job;
+        job.add_image(labels, mh, mw, ds, (int)dec.parents.size(), crops);
+        if (!enqueue_box_job(c, job, st)) return nullptr;
+    }
     PHD_HIPN(hipMemcpyAsync(h.data() + R.part2, dr + R.part2, R.total - R.part2, hipMemcpyDeviceToHost, st));
     PHD_HIPN(hipStreamSynchronize(st));
     for (int ch = 0; ch < 3; ch++) {
@@ -247,6 +261,7 @@ Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int heigh
                                      (const unsigned long long*)(h.data() + R.bins), fmax, cfg, crops,
                                      (const double*)(h.data() + R.sharp), &why, bscale);
     if (!out) set_error(why);
+    else if (box_pal) (void)box_palette_fill(box_pal, ncrops, (int)dec.parents.size(), (const uint32_t*)c->h_boxpal);
     return out;
 }
 

@@ -362,6 +362,7 @@ struct ReportArgs {
     hipStream_t stream;
     const Crop_Boundaries* const* img_crops;
     uint16_t* const* labels;                                  // per-image label maps (device) or NULL
+    phd_box_palette* const* box_pal;                          // per-image box palettes (host structs) or NULL
 };
 
 // How a call's FFT chain is launched: a row and a column launch per image, or
@@ -406,7 +407,15 @@ struct ReportRun : ReportArgs {
     uint8_t* hc() const { return hp + (size_t)n * L.a_bytes; }   // the C records on the host
 
     bool plan(), k1(), fft_chain(), palette_tail(), downloads(), assemble_groups(), timings();
-    bool label_maps();                                        // palette_tail()'s last step when labels != NULL
+    bool label_maps();                                        // palette_tail()'s last step: maps and box counts
+    bool label_launches(const std::vector<LabelDst>& dst, bool aligned);
+    // box palettes: image i's boxes are counted (it has a decision, a struct
+    // and boxes); where its counters start in Context::h_boxpal (-1: none)
+    bool counts_boxes(int i) const {
+        return box_pal && box_pal[i] && ok[i] && img_crops && img_crops[i] && img_crops[i]->N > 0;
+    }
+    std::vector<long long> bp_off;
+    bool box_palettes();                                      // the last stage: the structs of the reported images
 };
 
 // Validation, tables, FFT selection, layout, buffers, the shared-box array.
@@ -687,7 +696,7 @@ bool ReportRun::palette_tail() {
     if (!launch_palette_tail(c, L, n, d_imgs, height, width, ds, gp, cls, nchunks, fused, dec.data(), ok.data(), n_ent,
                              max_slots, max_per_img, s2))
         return false;
-    if (labels && !label_maps()) return false;
+    if ((labels || box_pal) && !label_maps()) return false;
     PHD_HIP(hipEventRecord(c->ev_tail, s2));
     return true;
 }
@@ -697,15 +706,52 @@ bool ReportRun::palette_tail() {
 // groups' cutoff and last pixel in the B records): one launch over the run
 // where that pass is batched, else one launch per image.  ev_tail follows, so
 // the call's last download -- which the call waits for -- is behind the maps.
+//
+// Box palettes: an image whose boxes are counted and that has no map of the
+// caller's gets one in the context's scratch (d_labscratch: 2 * mh * mw bytes
+// per such image of the run at 256-byte steps), written by the same launches;
+// the counting launch and its one download (enqueue_box_job) follow them on
+// the tail stream, so the counters are on the host when the call's last
+// download is.
 bool ReportRun::label_maps() {
+    const int mh = ds > 1 ? height / ds : height, mw = ds > 1 ? width / ds : width;
+    std::vector<uint16_t*> map(n, nullptr);
+    const size_t one = al(sizeof(uint16_t) * (size_t)mh * mw);
+    size_t scratch = 0;
+    for (int i = 0; i < n; i++) {
+        if (labels && ok[i]) map[i] = labels[i];
+        if (!map[i] && counts_boxes(i)) scratch += one;
+    }
+    if (scratch) {
+        if (!ensure_device(&c->d_labscratch, &c->labscratch_bytes, scratch)) return false;
+        uint8_t* p = (uint8_t*)c->d_labscratch;
+        for (int i = 0; i < n; i++)
+            if (!map[i] && counts_boxes(i)) {
+                map[i] = (uint16_t*)p;
+                p += one;
+            }
+    }
     std::vector<LabelDst> dst;
     bool aligned = true;
     for (int i = 0; i < n; i++) {
-        if (!labels[i] || !ok[i]) continue;
-        dst.push_back(LabelDst{labels[i], i, 0});
+        if (!map[i]) continue;
+        dst.push_back(LabelDst{map[i], i, 0});
         aligned = aligned && (reinterpret_cast<uintptr_t>(d_imgs[i]) & 3) == 0;
     }
     if (dst.empty()) return true;
+    if (!label_launches(dst, aligned)) return false;
+    if (!box_pal) return true;
+    BoxJob job;
+    bp_off.assign(n, -1);
+    for (int i = 0; i < n; i++) {
+        if (!counts_boxes(i)) continue;
+        bp_off[i] = job.counters;
+        job.add_image(map[i], mh, mw, ds, (int)c->dec_scratch[i].parents.size(), img_crops[i]);
+    }
+    return job.recs.empty() || enqueue_box_job(c, job, s2);
+}
+
+bool ReportRun::label_launches(const std::vector<LabelDst>& dst, bool aligned) {
     if (palette_tail_batched(gp, ds, fused, max_slots)) {
         const size_t bytes = sizeof(LabelDst) * dst.size();
         if (!upload_table(c, dst.data(), bytes, bytes, s2)) return false;
@@ -846,14 +892,31 @@ bool ReportRun::timings() {
     return true;
 }
 
+// The box palette structs of the reported images, from the counters the run's
+// streams brought to Context::h_boxpal (timings() has waited for them): n_slots
+// for each, the counts where the image has boxes.  A failed image keeps
+// {0, 0, NULL}.
+bool ReportRun::box_palettes() {
+    if (!box_pal) return true;
+    for (int i = 0; i < n; i++) {
+        if (!box_pal[i] || !out[i]) continue;
+        const bool counted = counts_boxes(i) && !bp_off.empty() && bp_off[i] >= 0;
+        if (!box_palette_fill(box_pal[i], counted ? img_crops[i]->N : 0, (int)c->dec_scratch[i].parents.size(),
+                              counted ? (const uint32_t*)c->h_boxpal + bp_off[i] : nullptr))
+            return false;
+    }
+    return true;
+}
+
 }  // namespace
 
 bool run_reports(Context* c, const uint8_t* const* d_imgs, int n, int height, int width,
                  const phd_config& cfg, const Crop_Boundaries* crops, Full_Report_Data** out, int* status,
-                 hipStream_t stream, const Crop_Boundaries* const* img_crops, uint16_t* const* labels) {
-    ReportRun r(ReportArgs{c, d_imgs, n, height, width, cfg, crops, out, status, stream, img_crops, labels});
+                 hipStream_t stream, const Crop_Boundaries* const* img_crops, uint16_t* const* labels,
+                 phd_box_palette* const* box_pal) {
+    ReportRun r(ReportArgs{c, d_imgs, n, height, width, cfg, crops, out, status, stream, img_crops, labels, box_pal});
     return r.plan() && r.k1() && r.fft_chain() && r.palette_tail() && r.downloads() && r.assemble_groups() &&
-           r.timings() && r.failures == 0;
+           r.timings() && r.box_palettes() && r.failures == 0;
 }
 
 bool run_palette_trace(Context* c, const uint8_t* d_img, int height, int width, const phd_config& cfg,

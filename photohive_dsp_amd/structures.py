@@ -1,7 +1,7 @@
 """ctypes mirrors of the C structs (layouts of /root/reference/structures.py:6-106,
 byte-identical to include/photohive_dsp.h), plus the new phd_config."""
 import ctypes
-from ctypes import POINTER, Structure, c_double, c_float, c_int, c_int64, c_uint, c_void_p
+from ctypes import POINTER, Structure, c_double, c_float, c_int, c_int64, c_uint, c_uint32, c_void_p
 
 Pixel = c_double
 
@@ -100,6 +100,12 @@ class PhdYuvView(Structure):
                 ("c_row_stride", c_int64), ("c_pixel_stride", c_int64),
                 ("chroma_shift_x", c_int), ("chroma_shift_y", c_int),
                 ("matrix", c_int), ("range", c_int), ("chroma", c_int)]
+
+
+class PhdBoxPalette(Structure):
+    """The box palette of one label map (include/photohive_dsp.h: phd_box_palette): counts is
+    n_boxes x (n_slots + 1) uint32, row-major, owned by the library until phd_free_box_palettes."""
+    _fields_ = [("n_boxes", c_int), ("n_slots", c_int), ("counts", POINTER(c_uint32))]
 
 
 # phd_yuv_view.matrix, .range and .chroma
