@@ -601,6 +601,85 @@ int phd_report_batch_device_yuv_box_palettes(const phd_yuv_view* views, int n_im
 int phd_debug_box_counts_host(const uint16_t* map, int mh, int mw, int n_slots,
                               const Crop_Boundaries* boxes, uint32_t* counts);
 
+/* ---- box statistics ------------------------------------------------------------
+ * The box statistics of an image are, per crop box, what get_rgb_statistics
+ * (src/image_processing.c:543-553) and get_hsv_average (src/image_processing.c:
+ * 533-540) over rgb2hsv's s (src/image_processing.c:372-417) give on
+ * crop_image(image, right, left, bottom, top) (src/image_processing.c:244-266)
+ * of the FULL-RESOLUTION image: rows top <= y < bottom, columns left <= x <
+ * right; downsample_rate plays no part, as it plays none in get_rgb_statistics
+ * or in the sharpness.  For 8-bit images the library keeps exact integers per
+ * box -- M[0..2] = sum k and M[3..5] = sum k^2 per channel, D[m] = sum of
+ * (max - min) over the pixels whose max is m, n1 = #(min == 0 < max), N pixels
+ * -- and finishes them as the report's own statistics are finished:
+ *   stats = the report's moment formula on (M, N): a whole-image box gives the
+ *           report's rgb_stats bit for bit;
+ *   S = sum over m = 1..255, ascending and sequential, of (double)D[m] / (double)m;
+ *   average_saturation = (S - (1.0 - 0.999999) * (double)n1) / (double)N.
+ * The sums come from integer atomics: the same on every run.  Typed views that
+ * are not 8-bit take the fp64 functions themselves (mean sum / N, the variance's
+ * second pass sum (x - B)^2 / N, s per pixel), summed in a fixed order. */
+typedef struct phd_box_stats {
+    int n_boxes;                 /* crops[i]->N; 0 when image i has no boxes */
+    RGB_Statistics* stats;       /* n_boxes; NULL when n_boxes == 0 */
+    double* average_saturation;  /* n_boxes; same malloc as stats */
+} phd_box_stats;
+/* Frees stats (and with it average_saturation) and zeroes the structs; bs ==
+ * NULL is a no-op. */
+void phd_free_box_stats(phd_box_stats* bs, int n);
+
+/* The stage alone (get_rgb_statistics, src/image_processing.c:543-553, and
+ * rgb2hsv + get_hsv_average, :372-417 and :533-540, on the boxes crop_image
+ * cuts, :244-266): n_images packed RGB8 device images of any sizes from 1 x 1
+ * and any base alignment.  boxes[i] NULL or N == 0 gives n_boxes 0.  Boxes
+ * follow the rule of the report's crops (inside the image, not empty, not
+ * inverted).  Anything else -- a NULL image, a non-positive size, a bad box
+ * list -- fails the call with -1 before any device work, phd_last_error naming
+ * image and box, and out is left zeroed.  One counting launch for all boxes of
+ * all images (and one small finish launch), on `stream` or (NULL) the
+ * library's, waited for in both cases.  No byte outside an image's 3 * H * W
+ * is read.  out: n_images structs (release with phd_free_box_stats).  0 or -1. */
+int phd_box_stats_device(const uint8_t* const* d_images, const int* heights, const int* widths, int n_images,
+                         const Crop_Boundaries* const* boxes, phd_box_stats* out, void* stream);
+
+/* The four _box_palettes entries plus box statistics (get_rgb_statistics,
+ * src/image_processing.c:543-553, and get_hsv_average, :533-540, on the boxes of
+ * :244-266): box_stats, n_images structs, receives image i's box statistics
+ * for the same `crops` that feed its sharpnesses and box palettes, in image
+ * coordinates, validated once by the same rule.  box_stats == NULL is exactly
+ * the _box_palettes call.  d_labels and box_palettes may be NULL independently:
+ * box statistics alone cause no label map, no scratch map and no label launch.
+ * An image without boxes gets {0, NULL, NULL} and no work; an image that fails
+ * for any reason fails alone, as in the _box_palettes call, and gets {0, NULL,
+ * NULL}.  The statistics are complete when the call returns (release with
+ * phd_free_box_stats) and do not depend on lanes, batch or run. */
+int phd_report_batch_device_mixed_box_stats(const uint8_t* const* d_images, const int* heights, const int* widths,
+                                            int n_images, const phd_config* cfg,
+                                            const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
+                                            phd_box_palette* box_palettes, phd_box_stats* box_stats,
+                                            Full_Report_Data** out, int* status, void* stream);
+int phd_report_batch_device_views_box_stats(const phd_image_view* views, int n_images, const phd_config* cfg,
+                                            const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
+                                            phd_box_palette* box_palettes, phd_box_stats* box_stats,
+                                            Full_Report_Data** out, int* status, void* stream);
+int phd_report_batch_device_typed_views_box_stats(const phd_typed_view* views, int n_images, const phd_config* cfg,
+                                                  const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
+                                                  phd_box_palette* box_palettes, phd_box_stats* box_stats,
+                                                  Full_Report_Data** out, int* status, void* stream);
+int phd_report_batch_device_yuv_box_stats(const phd_yuv_view* views, int n_images, const phd_config* cfg,
+                                          const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
+                                          phd_box_palette* box_palettes, phd_box_stats* box_stats,
+                                          Full_Report_Data** out, int* status, void* stream);
+
+/* Validation hook, host only (no GPU): the box statistics kernel's own item
+ * plan and row code (box_stat_tiles.h; get_rgb_statistics, src/image_processing.c:
+ * 543-553, and get_hsv_average, :533-540, on the boxes of :244-266) over one
+ * packed RGB8 image of host memory at any alignment.  stats and
+ * average_saturation: boxes->N each.  sums (or NULL): 264 unsigned long long per
+ * box = M[6], n1, N, D[256].  0, or -1 with phd_last_error. */
+int phd_debug_box_stats_host(const uint8_t* rgb, int height, int width, const Crop_Boundaries* boxes,
+                             RGB_Statistics* stats, double* average_saturation, unsigned long long* sums);
+
 /* Palette intermediates of one device-resident image, for bit-exact checks:
  * hist[TL] (arm_octree quantities), parents[*n_parents] (valid_parents in
  * palette order), kept[*n_parents] (pixels surviving group_irregular_pixels).
@@ -711,7 +790,8 @@ int phd_last_timings(double* ms, int n);
  * every launch of the kernels in `mask` (bit k = kernel k: 0 hsv_stats,
  * 1 fft_rows, 2 fft_cols, 3 palette_cutoffs, 4 palette_sums, 5 sharpness,
  * 6 pack_views, 7 classify_views, 8 decode_views, 9 yuv_views,
- * 10 palette_labels, 11 box_palettes).
+ * 10 palette_labels, 11 box_palettes, 12 box_stats, 13 the fp64 route's
+ * planar_box_stats).
  * phd_profile_kernels resets the counters; phd_profile_read returns the
  * accumulated milliseconds and launch count of one kernel. */
 int phd_profile_kernels(unsigned mask);

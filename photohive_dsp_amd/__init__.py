@@ -1,7 +1,8 @@
 """PhotoHive_DSP for MI355X: drop-in get_report / Report / set_bounding_boxes
 backed by hand-written HIP kernels (PhotoHive_DSP_lib/libreport_data.so)."""
-from .core import (Report, box_palettes_device, convert_yuv_device, decode_views_device, get_report, get_reports,  # noqa: F401
-                   make_typed_views, make_views, make_yuv_views, nv12_planes, pack_views_device, quantize_device,
-                   report_device, reports_device_labels, reports_device_mixed, reports_device_typed,
-                   reports_device_views, reports_device_yuv, set_bounding_boxes, sharpness_device)
+from .core import (Report, box_palettes_device, box_stats_device, convert_yuv_device,  # noqa: F401
+                   decode_views_device, get_report, get_reports, make_typed_views, make_views, make_yuv_views,
+                   nv12_planes, pack_views_device, quantize_device, report_device, reports_device_labels,
+                   reports_device_mixed, reports_device_typed, reports_device_views, reports_device_yuv,
+                   set_bounding_boxes, sharpness_device)
 from .lib import configure_hw_queues  # noqa: F401  (opt-in GPU_MAX_HW_QUEUES, before HIP starts)

@@ -20,8 +20,8 @@ import numpy as np
 from .lib import last_error, lib
 from .structures import (PHD_ELEM_F16, PHD_ELEM_F32, PHD_ELEM_F64, PHD_ELEM_U8, PHD_ELEM_U16, PHD_VIEW_SNAP_U8,
                          PHD_YUV_BT601, PHD_YUV_BT709, PHD_YUV_CHROMA_REPLICATE, PHD_YUV_CHROMA_TRIANGLE,
-                         PHD_YUV_FULL, PHD_YUV_LIMITED, Crop_Boundaries, Full_Report_Data, PhdBoxPalette, PhdConfig,
-                         PhdImageView, PhdTypedView, PhdYuvView, Pixel_HSV, RGB_Statistics)
+                         PHD_YUV_FULL, PHD_YUV_LIMITED, Crop_Boundaries, Full_Report_Data, PhdBoxPalette, PhdBoxStats,
+                         PhdConfig, PhdImageView, PhdTypedView, PhdYuvView, Pixel_HSV, RGB_Statistics)
 from .utils import hsv_to_rgb, image_pgm_to_pillow, to_rgb8
 
 DEFAULTS = dict(h_partitions=18, s_partitions=2, v_partitions=3, black_thresh=0.1, gray_thresh=0.1,
@@ -321,7 +321,7 @@ def reports_device_mixed(images, stream=None, salient_characters=None, **kw):
     return _run_reports(call, "reports_device_mixed", n, list(zip(hs, ws)), kw)
 
 
-def reports_device_labels(images, stream=None, salient_characters=None, box_palettes=False, **kw):
+def reports_device_labels(images, stream=None, salient_characters=None, box_palettes=False, box_stats=False, **kw):
     """reports_device_mixed plus each image's palette label map
     (phd_report_batch_device_mixed_labels).  images: a list of uint8 [H, W, 3]
     device tensors of any sizes, or one [N, H, W, 3] tensor.  Returns (reports,
@@ -332,7 +332,11 @@ def reports_device_labels(images, stream=None, salient_characters=None, box_pale
     kept.  box_palettes=True: returns (reports, labels, palettes), palettes[i]
     the image's box palette for its salient_characters boxes (image
     coordinates) as box_palettes_device returns it
-    (phd_report_batch_device_mixed_box_palettes)."""
+    (phd_report_batch_device_mixed_box_palettes).  box_stats=True: the images'
+    box statistics are appended last to the result, per image a float64
+    [n_boxes, 7] array (Br Bg Bb Cr Cg Cb and the average saturation of each
+    salient_characters box at full resolution) as box_stats_device returns it
+    (phd_report_batch_device_mixed_box_stats)."""
     import torch
     if isinstance(images, torch.Tensor):
         if images.dim() != 4:
@@ -347,7 +351,7 @@ def reports_device_labels(images, stream=None, salient_characters=None, box_pale
     cfg = make_config(**kw)
     crops = normalize_salient(salient_characters, n)
     if n == 0:
-        return ([], [], []) if box_palettes else ([], [])
+        return ([],) * (2 + bool(box_palettes) + bool(box_stats))
     r = max(1, int(cfg.downsample_rate))
     sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
     labels = [torch.empty((h // r, w // r) if r > 1 else (h, w), dtype=torch.int16, device=im.device)
@@ -362,17 +366,24 @@ def reports_device_labels(images, stream=None, salient_characters=None, box_pale
         lib.phd_report_batch_device_mixed_labels(ptrs, hs, ws, n, ctypes.byref(cfg), crops[0] if crops else None,
                                                  maps, outs, st, s)
 
-    if not box_palettes:
+    if not box_palettes and not box_stats:
         return _run_reports(call, "reports_device_labels", n, sizes, kw), labels
-    bp = (PhdBoxPalette * n)()
+    bp = (PhdBoxPalette * n)() if box_palettes else None
+    bs = (PhdBoxStats * n)() if box_stats else None
     try:
-        reps = _run_reports(lambda outs, st: lib.phd_report_batch_device_mixed_box_palettes(
-            ptrs, hs, ws, n, ctypes.byref(cfg), crops[0] if crops else None, maps, bp, outs, st, s),
-            "reports_device_labels", n, sizes, kw)
+        if box_stats:
+            reps = _run_reports(lambda outs, st: lib.phd_report_batch_device_mixed_box_stats(
+                ptrs, hs, ws, n, ctypes.byref(cfg), crops[0] if crops else None, maps, bp, bs, outs, st, s),
+                "reports_device_labels", n, sizes, kw)
+        else:
+            reps = _run_reports(lambda outs, st: lib.phd_report_batch_device_mixed_box_palettes(
+                ptrs, hs, ws, n, ctypes.byref(cfg), crops[0] if crops else None, maps, bp, outs, st, s),
+                "reports_device_labels", n, sizes, kw)
     except RuntimeError:
-        lib.phd_free_box_palettes(bp, n)
+        _free_boxes(bp, bs, n)
         raise
-    return reps, labels, _take_box_palettes(bp, n)
+    return (reps, labels) + ((_take_box_palettes(bp, n),) if box_palettes else ()) + \
+        ((_take_box_stats(bs, n),) if box_stats else ())
 
 
 def quantize_device(labels, reports, none_rgb=(0, 0, 0), stream=None):
@@ -427,6 +438,61 @@ def _take_box_palettes(bp, n):
         lib.phd_free_box_palettes(bp, n)
 
 
+def _free_boxes(bp, bs, n):
+    if bp is not None:
+        lib.phd_free_box_palettes(bp, n)
+    if bs is not None:
+        lib.phd_free_box_stats(bs, n)
+
+
+def _take_box_stats(bs, n):
+    """The numpy copies of n filled phd_box_stats structs (float64 [n_boxes, 7]
+    each: Br Bg Bb Cr Cg Cb, average saturation); the C blocks are freed."""
+    try:
+        out = []
+        for i in range(n):
+            nb = int(bs[i].n_boxes)
+            a = np.zeros((nb, 7), dtype=np.float64)
+            if nb:
+                st = np.ctypeslib.as_array(ctypes.cast(bs[i].stats, ctypes.POINTER(ctypes.c_double)), shape=(nb, 6))
+                a[:, :6] = st
+                a[:, 6] = np.ctypeslib.as_array(bs[i].average_saturation, shape=(nb,))
+            out.append(a)
+        return out
+    finally:
+        lib.phd_free_box_stats(bs, n)
+
+
+def box_stats_device(images, boxes, stream=None):
+    """The box statistics of packed uint8 [H, W, 3] device tensors of any sizes
+    (phd_box_stats_device): per image a numpy.float64 [n_boxes, 7] array, row b
+    the brightness Br Bg Bb, the contrast Cr Cg Cb and the average saturation
+    of the pixels of box b at full resolution -- what get_rgb_statistics and
+    get_hsv_average give on the cropped image.  boxes: what normalize_salient
+    accepts, in image coordinates (rows top <= y < bottom, columns left <= x <
+    right; None or an empty list: no boxes, an array of shape (0, 7)).  One
+    launch sums every box of every image."""
+    import torch
+    if isinstance(images, torch.Tensor) and images.dim() == 4:
+        images = list(images.unbind(0))
+    images = list(images)
+    for im in images:
+        if not isinstance(im, torch.Tensor) or im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 \
+                or not im.is_contiguous() or im.numel() == 0:
+            raise ValueError("expected contiguous, non-empty uint8 [H, W, 3] device tensors")
+    n = len(images)
+    crops = normalize_salient(boxes if boxes is not None else [None] * n, n)
+    if n == 0:
+        return []
+    ptrs = (ctypes.c_void_p * n)(*[im.data_ptr() for im in images])
+    hs = (ctypes.c_int * n)(*[int(im.shape[0]) for im in images])
+    ws = (ctypes.c_int * n)(*[int(im.shape[1]) for im in images])
+    bs = (PhdBoxStats * n)()
+    if lib.phd_box_stats_device(ptrs, hs, ws, n, crops[0], bs, _stream_handle(stream)) != 0:
+        raise RuntimeError(f"box_stats_device failed: {last_error()}")
+    return _take_box_stats(bs, n)
+
+
 def box_palettes_device(labels, reports_or_n_slots, boxes, stream=None):
     """The box palettes of label maps (phd_box_palettes_device): per map a
     numpy.uint32 [n_boxes, n_slots + 1] array; row b, column s is the number of
@@ -460,20 +526,22 @@ def box_palettes_device(labels, reports_or_n_slots, boxes, stream=None):
 
 
 def _report_views(entry, name, views, n, stream, salient_characters, kw, label_entry=None, devices=None,
-                  box_entry=None):
+                  box_entry=None, stats_entry=None):
     """reports_device_views, _typed and _yuv after their descriptors are made.
     devices (labels=True): the maps are allocated here as reports_device_labels
     allocates its own, image i's on devices[i], and filled by label_entry, the
     entry's _labels form.  box_entry (box_palettes=True): its _box_palettes
     form; the box palettes are appended to the result.  Returns the reports,
-    (reports, maps), (reports, palettes) or (reports, maps, palettes)."""
+    (reports, maps), (reports, palettes) or (reports, maps, palettes).
+    stats_entry (box_stats=True): the entry's _box_stats form, which takes the
+    box palettes too (or none); the box statistics are appended last."""
     cfg = make_config(**kw)
     crops = normalize_salient(salient_characters, n)
     want_maps = devices is not None
-    if n == 0 and (want_maps or box_entry is not None):
-        return ([],) * (1 + want_maps + (box_entry is not None))
+    if n == 0 and (want_maps or box_entry is not None or stats_entry is not None):
+        return ([],) * (1 + want_maps + (box_entry is not None) + (stats_entry is not None))
     s = _stream_handle(stream)
-    if not want_maps and box_entry is None:
+    if not want_maps and box_entry is None and stats_entry is None:
         return _run_reports(lambda outs, st: entry(views, n, ctypes.byref(cfg), crops[0] if crops else None, outs, st,
                                                    s), name, n, _view_sizes(views, n), kw)
     sizes = _view_sizes(views, n)
@@ -484,18 +552,23 @@ def _report_views(entry, name, views, n, stream, salient_characters, kw, label_e
         labels = [torch.empty((h // r, w // r) if r > 1 else (h, w), dtype=torch.int16, device=dev)
                   for (h, w), dev in zip(sizes, devices)]
         maps = (ctypes.c_void_p * n)(*[m.data_ptr() for m in labels])
-    if box_entry is None:
+    if box_entry is None and stats_entry is None:
         return _run_reports(lambda outs, st: label_entry(views, n, ctypes.byref(cfg), crops[0] if crops else None,
                                                          maps, outs, st, s), name, n, sizes, kw), labels
-    bp = (PhdBoxPalette * n)()
+    bp = (PhdBoxPalette * n)() if box_entry is not None else None
+    bs = (PhdBoxStats * n)() if stats_entry is not None else None
     try:
-        reps = _run_reports(lambda outs, st: box_entry(views, n, ctypes.byref(cfg), crops[0] if crops else None, maps,
-                                                       bp, outs, st, s), name, n, sizes, kw)
+        if stats_entry is not None:
+            reps = _run_reports(lambda outs, st: stats_entry(views, n, ctypes.byref(cfg), crops[0] if crops else None,
+                                                             maps, bp, bs, outs, st, s), name, n, sizes, kw)
+        else:
+            reps = _run_reports(lambda outs, st: box_entry(views, n, ctypes.byref(cfg), crops[0] if crops else None,
+                                                           maps, bp, outs, st, s), name, n, sizes, kw)
     except RuntimeError:
-        lib.phd_free_box_palettes(bp, n)
+        _free_boxes(bp, bs, n)
         raise
-    pals = _take_box_palettes(bp, n)
-    return (reps, labels, pals) if want_maps else (reps, pals)
+    return (reps,) + ((labels,) if want_maps else ()) + ((_take_box_palettes(bp, n),) if bp is not None else ()) + \
+        ((_take_box_stats(bs, n),) if bs is not None else ())
 
 
 def _label_devices(keep, tensor_of):
@@ -568,7 +641,7 @@ def make_views(tensors, layout="HWC", bgr=False):
 
 
 def reports_device_views(images, layout="HWC", bgr=False, stream=None, salient_characters=None, labels=False,
-                         box_palettes=False, **kw):
+                         box_palettes=False, box_stats=False, **kw):
     """Reports for uint8 device tensors in any byte-strided layout (make_views:
     planar CHW, pitched rows, RGBA / BGRA, BGR, regions of interest, expanded
     grey planes; any sizes), without a repacked copy on the caller's side:
@@ -584,15 +657,20 @@ def reports_device_views(images, layout="HWC", bgr=False, stream=None, salient_c
     palettes) or (reports, maps, palettes) -- per image a numpy.uint32
     [n_boxes, n_slots + 1] array as box_palettes_device returns it, for its
     salient_characters boxes (image coordinates); shape (0, n_slots + 1) for an
-    image without boxes (phd_report_batch_device_views_box_palettes)."""
+    image without boxes (phd_report_batch_device_views_box_palettes).
+    box_stats=True (independent of both): the images' box statistics are
+    appended last -- per image a float64 [n_boxes, 7] array (Br Bg Bb Cr Cg Cb
+    and the average saturation of each box at full resolution) as
+    box_stats_device returns it (phd_report_batch_device_views_box_stats)."""
     views, keep = make_views(images, layout, bgr)
-    if not labels and not box_palettes:
+    if not labels and not box_palettes and not box_stats:
         return _report_views(lib.phd_report_batch_device_views, "reports_device_views", views, len(keep), stream,
                              salient_characters, kw)
     return _report_views(None, "reports_device_views", views, len(keep), stream, salient_characters, kw,
                          lib.phd_report_batch_device_views_labels,
                          _label_devices(keep, lambda t: t) if labels else None,
-                         lib.phd_report_batch_device_views_box_palettes if box_palettes else None)
+                         lib.phd_report_batch_device_views_box_palettes if box_palettes else None,
+                         lib.phd_report_batch_device_views_box_stats if box_stats else None)
 
 
 def pack_views_device(images, layout="HWC", bgr=False, stream=None):
@@ -653,7 +731,7 @@ def make_typed_views(tensors, layout="HWC", bgr=False, max_value=None, snap_u8=F
 
 
 def reports_device_typed(images, layout="HWC", bgr=False, max_value=None, snap_u8=False, stream=None,
-                         salient_characters=None, labels=False, box_palettes=False, **kw):
+                         salient_characters=None, labels=False, box_palettes=False, box_stats=False, **kw):
     """Reports for device tensors of any element type in any byte-strided layout
     (make_typed_views; any sizes): a 16-bit decode, a float CHW tensor in 0..1,
     double planes already on the GPU.  Images whose values are exactly 8-bit
@@ -667,15 +745,19 @@ def reports_device_typed(images, layout="HWC", bgr=False, max_value=None, snap_u
     (phd_report_batch_device_typed_views_labels): an 8-bit image's map is that
     of its bytes, an fp64-route image's the reference's lists on its doubles.
     box_palettes=True: the box palettes are appended as reports_device_views
-    appends them (phd_report_batch_device_typed_views_box_palettes)."""
+    appends them (phd_report_batch_device_typed_views_box_palettes).
+    box_stats=True: the box statistics are appended last as
+    reports_device_views appends them; an fp64-route image's are the fp64
+    functions on its doubles (phd_report_batch_device_typed_views_box_stats)."""
     views, keep = make_typed_views(images, layout, bgr, max_value, snap_u8)
-    if not labels and not box_palettes:
+    if not labels and not box_palettes and not box_stats:
         return _report_views(lib.phd_report_batch_device_typed_views, "reports_device_typed", views, len(keep),
                              stream, salient_characters, kw)
     return _report_views(None, "reports_device_typed", views, len(keep), stream, salient_characters, kw,
                          lib.phd_report_batch_device_typed_views_labels,
                          _label_devices(keep, lambda t: t) if labels else None,
-                         lib.phd_report_batch_device_typed_views_box_palettes if box_palettes else None)
+                         lib.phd_report_batch_device_typed_views_box_palettes if box_palettes else None,
+                         lib.phd_report_batch_device_typed_views_box_stats if box_stats else None)
 
 
 def decode_views_device(images, layout="HWC", bgr=False, max_value=None, stream=None):
@@ -773,7 +855,7 @@ def make_yuv_views(frames, matrix="bt601", full_range=True, chroma="replicate", 
 
 
 def reports_device_yuv(frames, matrix="bt601", full_range=True, chroma="replicate", swap_uv=False, stream=None,
-                       salient_characters=None, labels=False, box_palettes=False, **kw):
+                       salient_characters=None, labels=False, box_palettes=False, box_stats=False, **kw):
     """Reports for 8-bit YCbCr frames on the current GPU (make_yuv_views: NV12
     surfaces, planar 4:2:0 / 4:2:2 / 4:4:4, YUY2 descriptors; any sizes): each
     frame is converted to RGB8 by the library's integer conversion
@@ -784,15 +866,18 @@ def reports_device_yuv(frames, matrix="bt601", full_range=True, chroma="replicat
     coordinates, on the luma plane's device (phd_report_batch_device_yuv_labels;
     the frames must be tensors).  box_palettes=True: the box palettes are
     appended as reports_device_views appends them
-    (phd_report_batch_device_yuv_box_palettes)."""
+    (phd_report_batch_device_yuv_box_palettes).  box_stats=True: the box
+    statistics of the RGB8 conversion are appended last as reports_device_views
+    appends them (phd_report_batch_device_yuv_box_stats)."""
     views, keep = make_yuv_views(frames, matrix, full_range, chroma, swap_uv)
-    if not labels and not box_palettes:
+    if not labels and not box_palettes and not box_stats:
         return _report_views(lib.phd_report_batch_device_yuv, "reports_device_yuv", views, len(keep), stream,
                              salient_characters, kw)
     return _report_views(None, "reports_device_yuv", views, len(keep), stream, salient_characters, kw,
                          lib.phd_report_batch_device_yuv_labels,
                          _label_devices(keep, lambda f: f[0] if isinstance(f, (tuple, list)) else f) if labels
-                         else None, lib.phd_report_batch_device_yuv_box_palettes if box_palettes else None)
+                         else None, lib.phd_report_batch_device_yuv_box_palettes if box_palettes else None,
+                         lib.phd_report_batch_device_yuv_box_stats if box_stats else None)
 
 
 def convert_yuv_device(frames, matrix="bt601", full_range=True, chroma="replicate", swap_uv=False, stream=None):

@@ -582,6 +582,11 @@ void destroy_context(Context* c) {
     dfree(c->d_labscratch);
     if (c->h_boxpal) (void)hipHostFree(c->h_boxpal);
     c->h_boxpal = nullptr;
+    dfree(c->d_boxstat);
+    c->boxstat_bytes = 0;
+    if (c->h_boxstat) (void)hipHostFree(c->h_boxstat);
+    c->h_boxstat = nullptr;
+    c->h_boxstat_bytes = 0;
     for (auto& p : c->d_stage2) dfree(p);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     c->h_pin = nullptr;

@@ -507,7 +507,8 @@ void report_group(Context* cl, const std::vector<BatchImage>& imgs, const std::v
     std::vector<const Crop_Boundaries*> cr(m);
     std::vector<uint16_t*> lab(m);
     std::vector<phd_box_palette*> bp(m);
-    bool maps = false, pals = false;
+    std::vector<phd_box_stats*> bs(m);
+    bool maps = false, pals = false, stats = false;
     for (int q = 0; q < m; q++) {
         rp[q] = ptrs[ks[q]];
         cr[q] = imgs[grp[ks[q]]].boxes;
@@ -515,11 +516,13 @@ void report_group(Context* cl, const std::vector<BatchImage>& imgs, const std::v
         bp[q] = imgs[grp[ks[q]]].box_pal;
         maps = maps || lab[q];
         pals = pals || bp[q];
+        bs[q] = imgs[grp[ks[q]]].box_stats;
+        stats = stats || bs[q];
     }
     RunResults rr(m);
     run_reports(cl, rp.data(), m, imgs[grp[0]].height, imgs[grp[0]].width, cfg, nullptr, rr.o.data(), rr.st.data(),
                 (hipStream_t)stream, boxes ? cr.data() : nullptr, maps ? lab.data() : nullptr,
-                pals ? bp.data() : nullptr);
+                pals ? bp.data() : nullptr, stats ? bs.data() : nullptr);
     for (int q = 0; q < m; q++) {
         r->o[ks[q]] = rr.o[q];
         r->st[ks[q]] = rr.st[q];
@@ -607,10 +610,12 @@ extern "C" int phd_report_batch_device_crops(const uint8_t* d_rgb, int n_images,
 static int report_mixed(const char* entry, const uint8_t* const* d_images, const int* heights, const int* widths,
                         int n_images, const phd_config* cfg, const Crop_Boundaries* const* crops,
                         Full_Report_Data** out, int* status, void* stream, uint16_t* const* d_labels = nullptr,
-                        phd_box_palette* box_palettes = nullptr) {
+                        phd_box_palette* box_palettes = nullptr, phd_box_stats* box_stats = nullptr) {
     clear_error();
     if (box_palettes && n_images > 0)
         for (int i = 0; i < n_images; i++) box_palettes[i] = phd_box_palette{0, 0, nullptr};
+    if (box_stats && n_images > 0)
+        for (int i = 0; i < n_images; i++) box_stats[i] = phd_box_stats{0, nullptr, nullptr};
     if (!d_images || !heights || !widths || !cfg || !out || !status || n_images <= 0) {
         set_error(std::string(entry) + ": bad arguments");
         return -1;
@@ -625,7 +630,8 @@ static int report_mixed(const char* entry, const uint8_t* const* d_images, const
     std::vector<BatchImage> imgs;
     for (int i : valid_box_images(crops, heights, widths, 0, 0, n_images, out, status))
         imgs.push_back({i, BatchImage::kPacked, d_images[i], heights[i], widths[i], crops ? crops[i] : nullptr,
-                        d_labels ? d_labels[i] : nullptr, box_palettes ? box_palettes + i : nullptr});
+                        d_labels ? d_labels[i] : nullptr, box_palettes ? box_palettes + i : nullptr,
+                        box_stats ? box_stats + i : nullptr});
     return run_device_batch(c, imgs, mixed_groups(imgs), run_packed_group, crops != nullptr, *cfg, out, status,
                             n_images, stream);
 }
@@ -669,6 +675,20 @@ extern "C" int phd_report_batch_device_mixed_box_palettes(const uint8_t* const* 
     return report_mixed(box_palettes ? "phd_report_batch_device_mixed_box_palettes"
                                      : "phd_report_batch_device_mixed_labels",
                         d_images, heights, widths, n_images, cfg, crops, out, status, stream, d_labels, box_palettes);
+}
+
+// ... plus each image's box statistics (ReportRun::box_stat_job, beside the
+// sharpness launch).  box_stats == NULL: exactly the call above.
+extern "C" int phd_report_batch_device_mixed_box_stats(const uint8_t* const* d_images, const int* heights,
+                                                       const int* widths, int n_images, const phd_config* cfg,
+                                                       const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
+                                                       phd_box_palette* box_palettes, phd_box_stats* box_stats,
+                                                       Full_Report_Data** out, int* status, void* stream) {
+    if (!box_stats)
+        return phd_report_batch_device_mixed_box_palettes(d_images, heights, widths, n_images, cfg, crops, d_labels,
+                                                          box_palettes, out, status, stream);
+    return report_mixed("phd_report_batch_device_mixed_box_stats", d_images, heights, widths, n_images, cfg, crops,
+                        out, status, stream, d_labels, box_palettes, box_stats);
 }
 
 extern "C" int phd_report_batch_u8_crops(const uint8_t* const* images, const int* heights, const int* widths,

@@ -18,6 +18,7 @@
 #include "phd_internal.h"
 #include "batch_plan.h"
 #include "box_tiles.h"
+#include "box_stat_tiles.h"
 #include "sharp_plan.h"
 #include "views_plan.h"
 #include "yuv_plan.h"
@@ -134,9 +135,11 @@ bool gfft_run(const GfftPlan& p, const double2* in, double2* out, long count, do
 // ---- per-kernel event timing (opt-in, phd_profile_kernels) -----------------
 enum KernelId {
     kK1 = 0, kFftRows = 1, kFftCols = 2, kCutoffs = 3, kPalSums = 4, kSharp = 5, kPack = 6, kClassify = 7,
-    kDecode = 8, kYuv = 9, kLabels = 10, kBoxPalettes = 11, kNumKernels = 12
+    kDecode = 8, kYuv = 9, kLabels = 10, kBoxPalettes = 11, kBoxStats = 12, kPlanarBoxStats = 13, kNumKernels = 14
 };
 static_assert(kBoxPalettes == kProfBoxPalettes, "the box palette launch's profiler slot");
+static_assert(kBoxStats == kProfBoxStats && kPlanarBoxStats == kProfPlanarBoxStats,
+              "the box statistics launches' profiler slots");
 static_assert(kClassify == kProfClassify && kDecode == kProfDecode, "the decode launches' profiler slots");
 static_assert(kYuv == kProfYuv, "the YUV conversion launch's profiler slot");
 static_assert(kLabels == kProfLabels, "the label map launch's profiler slot");
@@ -253,6 +256,14 @@ struct Context {
     size_t boxpal_bytes = 0;
     void* h_boxpal = nullptr;
     size_t h_boxpal_bytes = 0;
+    // box statistics (phd_boxstats.cpp): records | items | the boxes' sums | the
+    // finish's 64 bytes per box on the device, and the pinned block the table
+    // goes up from and those 64 bytes come down to (the fp64 route: its items
+    // and partial sums through the same pair)
+    void* d_boxstat = nullptr;
+    size_t boxstat_bytes = 0;
+    void* h_boxstat = nullptr;
+    size_t h_boxstat_bytes = 0;
     // the label maps of a run's images that have boxes to count and no map of
     // the caller's: 2 * mh * mw bytes each at 256-byte steps, grow-only
     void* d_labscratch = nullptr;
@@ -426,10 +437,12 @@ Full_Report_Data* report_planar(Context* c, const double* r, const double* g, co
 // it on the planes k_decode_view filled.  labels (or NULL): the image's palette
 // label map (device), complete when the call returns.  box_pal (or NULL): the
 // image's box palette (zeroed by the caller), counted from labels or from a
-// map in Context::d_labscratch.
+// map in Context::d_labscratch.  box_stats (or NULL): the image's box
+// statistics (zeroed by the caller) from the fp64 functions on the planes
+// (k_planar_box_stats, beside the sharpness crops); filled when the image reports.
 Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int height, int width, const phd_config& cfg,
                                        const Crop_Boundaries* crops, hipStream_t st, uint16_t* labels,
-                                       phd_box_palette* box_pal = nullptr);
+                                       phd_box_palette* box_pal = nullptr, phd_box_stats* box_stats = nullptr);
 // Run the full report on n same-size device images.  out[i]/status[i] per image.
 // crops: one set of boxes for every image (the single-image entries; two
 // launches per box, sharpness.hip's k_sharp_pass).  img_crops (crops must be
@@ -442,10 +455,14 @@ Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int heigh
 // allowed; zeroed by the caller): n_slots for every reported image, the counts
 // of its img_crops boxes where it has any -- from labels[i], or from a scratch
 // map of the context (Context::d_labscratch) where the caller gave none.
+// box_stats (or NULL): image i's box statistics go to *box_stats[i] (NULL
+// entries allowed; zeroed by the caller) from its img_crops boxes, enqueued with
+// the sharpness launch; a failed image keeps {0, NULL, NULL}.
 bool run_reports(Context* c, const uint8_t* const* d_imgs, int n, int height, int width,
                  const phd_config& cfg, const Crop_Boundaries* crops, Full_Report_Data** out,
                  int* status, hipStream_t stream, const Crop_Boundaries* const* img_crops = nullptr,
-                 uint16_t* const* labels = nullptr, phd_box_palette* const* box_pal = nullptr);
+                 uint16_t* const* labels = nullptr, phd_box_palette* const* box_pal = nullptr,
+                 phd_box_stats* const* box_stats = nullptr);
 // A launch table (phd_inputs.cpp): `bytes` go up on st into Context::d_views
 // through its pinned copy, the first `filled` from `host`, the rest zero, once
 // the last launch that read the table is done; table_launched: after the last
@@ -475,6 +492,25 @@ bool box_palette_fill(phd_box_palette* bp, int n_boxes, int n_slots, const uint3
 // by one memset, one launch counts, one copy brings the counters to
 // Context::h_boxpal.  The caller waits for st before it reads them.
 bool enqueue_box_job(Context* c, const BoxJob& job, hipStream_t st);
+// The box statistics of a launch (phd_boxstats.cpp; records and row walk:
+// box_stat_tiles.h): the boxes' records and box_plan's items.
+struct BoxStatJob {
+    std::vector<BoxStatRec> recs;
+    std::vector<BoxItem> items;
+    // the boxes of a packed RGB8 image of `width` columns (validated: crops_why)
+    void add_image(const uint8_t* img, int width, const Crop_Boundaries* b);
+};
+// The job on st: the table goes up from Context::h_boxstat, one memset zeroes
+// the records, k_box_stats (profile slot 12) and its finish run, one copy brings
+// kBoxStatOut u64 per box to Context::h_boxstat, where box_stats_host() points
+// after the caller has waited for st.
+bool enqueue_box_stat_job(Context* c, const BoxStatJob& job, hipStream_t st);
+const unsigned long long* box_stats_host(const Context* c);
+// *bs <- n_boxes boxes from their downloaded kBoxStatOut u64 each (h) and their
+// pixel counts (one malloc; none for no boxes)
+bool box_stats_fill(phd_box_stats* bs, const Crop_Boundaries* b, const unsigned long long* h);
+// the same from finished values: stats[k], average_saturation[k]
+bool box_stats_alloc(phd_box_stats* bs, int n_boxes);
 // A grow-only pinned block of at least `need` bytes (the old one is freed at once)
 bool grow_pinned(void** p, size_t* cap, size_t need);
 
@@ -491,6 +527,7 @@ struct BatchImage {
     const Crop_Boundaries* boxes;    // NULL: none
     uint16_t* labels = nullptr;      // device: the image's label map, (height / ds) x (width / ds); NULL: none
     phd_box_palette* box_pal = nullptr;   // the caller's struct for the image's box palette; NULL: none
+    phd_box_stats* box_stats = nullptr;   // the caller's struct for the image's box statistics; NULL: none
 };
 // The reports and statuses of one run of m images, and their way back to the
 // caller's arrays: result k belongs to the caller's image idx[k].

@@ -267,7 +267,7 @@ void run_typed_group(Context* cl, const std::vector<BatchImage>& imgs, const std
         if (enqueue_decode_view(cl, tv(k), dp, st))
             o = report_planes_device(cl, PlanarSrc{dp, dp + n, dp + 2 * n}, height, width, cfg,
                                      boxes ? imgs[grp[k]].boxes : nullptr, st, imgs[grp[k]].labels,
-                                     imgs[grp[k]].box_pal);
+                                     imgs[grp[k]].box_pal, imgs[grp[k]].box_stats);
         (void)hipStreamSynchronize(st);
         cl->prof.collect();
         if (o) {
@@ -291,10 +291,12 @@ template <class View, class Why>
 int report_views(const char* entry, BatchImage::Source kind, GroupFn run_group, const View* views, int n_images,
                  const phd_config* cfg, const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
                  Full_Report_Data** out, int* status, void* stream, Why view_ok,
-                 phd_box_palette* box_palettes = nullptr) {
+                 phd_box_palette* box_palettes = nullptr, phd_box_stats* box_stats = nullptr) {
     clear_error();
     if (box_palettes && n_images > 0)
         for (int i = 0; i < n_images; i++) box_palettes[i] = phd_box_palette{0, 0, nullptr};
+    if (box_stats && n_images > 0)
+        for (int i = 0; i < n_images; i++) box_stats[i] = phd_box_stats{0, nullptr, nullptr};
     if (!views || !cfg || !out || !status || n_images <= 0) {
         set_error(std::string(entry) + ": bad arguments");
         return -1;
@@ -312,7 +314,8 @@ int report_views(const char* entry, BatchImage::Source kind, GroupFn run_group, 
         std::string why;
         if (view_ok(views[i], &why) && (!crops || crops_why(crops[i], views[i].height, views[i].width, &why)))
             imgs.push_back({i, kind, &views[i], views[i].height, views[i].width, crops ? crops[i] : nullptr,
-                            d_labels ? d_labels[i] : nullptr, box_palettes ? box_palettes + i : nullptr});
+                            d_labels ? d_labels[i] : nullptr, box_palettes ? box_palettes + i : nullptr,
+                            box_stats ? box_stats + i : nullptr});
         else bad = "image " + std::to_string(i) + ": " + why;
     }
     Context* c = get_context();
@@ -451,6 +454,46 @@ extern "C" int phd_report_batch_device_typed_views_box_palettes(const phd_typed_
         return phd_report_batch_device_typed_views_labels(views, n_images, cfg, crops, d_labels, out, status, stream);
     return report_views("phd_report_batch_device_typed_views_box_palettes", BatchImage::kTyped, run_typed_group, views,
                         n_images, cfg, crops, d_labels, out, status, stream, typed_view_why, box_palettes);
+}
+
+// The three _box_palettes entries plus each image's box statistics (per crop
+// box, get_rgb_statistics and get_hsv_average of its pixels:
+// ReportRun::box_stat_job on the staged RGB8 images, report_planes_device on the
+// fp64 route).  box_stats == NULL: exactly the _box_palettes entry.
+extern "C" int phd_report_batch_device_views_box_stats(const phd_image_view* views, int n_images,
+                                                       const phd_config* cfg, const Crop_Boundaries* const* crops,
+                                                       uint16_t* const* d_labels, phd_box_palette* box_palettes,
+                                                       phd_box_stats* box_stats, Full_Report_Data** out, int* status,
+                                                       void* stream) {
+    if (!box_stats)
+        return phd_report_batch_device_views_box_palettes(views, n_images, cfg, crops, d_labels, box_palettes, out,
+                                                          status, stream);
+    return report_views("phd_report_batch_device_views_box_stats", BatchImage::kView, run_staged_group, views,
+                        n_images, cfg, crops, d_labels, out, status, stream, view_why, box_palettes, box_stats);
+}
+
+extern "C" int phd_report_batch_device_yuv_box_stats(const phd_yuv_view* views, int n_images, const phd_config* cfg,
+                                                     const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
+                                                     phd_box_palette* box_palettes, phd_box_stats* box_stats,
+                                                     Full_Report_Data** out, int* status, void* stream) {
+    if (!box_stats)
+        return phd_report_batch_device_yuv_box_palettes(views, n_images, cfg, crops, d_labels, box_palettes, out,
+                                                        status, stream);
+    return report_views("phd_report_batch_device_yuv_box_stats", BatchImage::kYuv, run_staged_group, views, n_images,
+                        cfg, crops, d_labels, out, status, stream, yuv_view_why, box_palettes, box_stats);
+}
+
+extern "C" int phd_report_batch_device_typed_views_box_stats(const phd_typed_view* views, int n_images,
+                                                             const phd_config* cfg,
+                                                             const Crop_Boundaries* const* crops,
+                                                             uint16_t* const* d_labels, phd_box_palette* box_palettes,
+                                                             phd_box_stats* box_stats, Full_Report_Data** out,
+                                                             int* status, void* stream) {
+    if (!box_stats)
+        return phd_report_batch_device_typed_views_box_palettes(views, n_images, cfg, crops, d_labels, box_palettes,
+                                                                out, status, stream);
+    return report_views("phd_report_batch_device_typed_views_box_stats", BatchImage::kTyped, run_typed_group, views,
+                        n_images, cfg, crops, d_labels, out, status, stream, typed_view_why, box_palettes, box_stats);
 }
 
 // (one decode launch per image)

@@ -291,6 +291,18 @@ struct BoxItem;
 hipError_t launch_box_counts(const BoxRec* d_recs, const BoxItem* d_items, int nitems, unsigned* d_counts,
                              hipStream_t st);
 
+// ---- box statistics (box_stats.hip; records and row walk: box_stat_tiles.h) ----
+// Per crop box of a packed RGB8 image the exact sums of its pixels: nitems items
+// of box_plan over the boxes d_recs, added into d_out (kBoxStatRec u64 per box,
+// zeroed by the caller).  The finish leaves kBoxStatOut u64 per box in d_fin:
+// the six moments, n1 and the bits of S.
+constexpr int kProfBoxStats = 12, kProfPlanarBoxStats = 13;
+struct BoxStatRec;
+hipError_t launch_box_stats(const BoxStatRec* d_recs, const BoxItem* d_items, int nitems, unsigned long long* d_out,
+                            hipStream_t st);
+hipError_t launch_box_stats_finish(const unsigned long long* d_rec, int nboxes, unsigned long long* d_fin,
+                                   hipStream_t st);
+
 // Row pass: luma - avg of two rows as one complex sequence, FFT, split, write
 // the half spectra column-major into inter[wf][height].
 // Runtime-plan FFT passes over a batch of same-size images in one launch each
@@ -504,6 +516,16 @@ constexpr int kProfPalSums = 4;
 // map, per hsv pixel its group's slot when the keep rule keeps it, else 0xFFFF.
 hipError_t launch_planar_labels(const PlanarSrc& P, int height, int width, int ds, const GridParams& gp,
                                 const GroupRule* rules, uint16_t* map, hipStream_t st);
+// The fp64 box statistics of the planes: one item per band of whole rows of a box
+// (box_plan's bands), `first` / `count` the items of its box and npix the box's
+// pixels.  Two launches: part1[4 * item + {r, g, b, s}] the items' sums, then
+// part2[3 * item + c] their sums of (x - B)^2 with the box's means B taken from
+// part1 in item order.  (k_planar_box_stats: profile slot 13)
+struct PlanarBoxItem {
+    int left, cols, row0, rows, first, count, npix, pad;
+};
+hipError_t launch_planar_box_stats(const PlanarSrc& P, int width, const PlanarBoxItem* d_items, int nitems,
+                                   double* part1, double* part2, hipStream_t st);
 
 // ---- global-memory batched FFTs and the generic 2-D path (fft_global.hip) ----
 // Blocks of the generic path's power / binning pass (= its max partials).

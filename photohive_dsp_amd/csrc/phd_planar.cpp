@@ -120,7 +120,7 @@ Full_Report_Data* report_planar(Context* c, const double* r, const double* g, co
 // the image fails before its palette decision.
 Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int height, int width, const phd_config& cfg,
                                        const Crop_Boundaries* crops, hipStream_t st, uint16_t* labels,
-                                       phd_box_palette* box_pal) {
+                                       phd_box_palette* box_pal, phd_box_stats* box_stats) {
     std::string why;
     const long n = (long)height * width;
     double* pgm = c->d_planes + 3 * n;
@@ -147,6 +147,27 @@ Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int heigh
     if (count_boxes && !labels) {
         if (!ensure_device(&c->d_labscratch, &c->labscratch_bytes, sizeof(uint16_t) * (size_t)mh * mw)) return nullptr;
         labels = (uint16_t*)c->d_labscratch;
+    }
+    // box statistics: box_plan's bands as items; device: items | part1 | part2,
+    // pinned: the items going up, then the two partial arrays coming down
+    std::vector<PlanarBoxItem> bs_items;
+    size_t bs_o1 = 0, bs_o2 = 0;
+    if (box_stats && ncrops > 0) {
+        std::vector<BoxItem> bands;
+        for (int k = 0; k < ncrops; k++) {
+            const int first = (int)bands.size(), cols = crops->right[k] - crops->left[k];
+            box_plan(k, crops->top[k], crops->bottom[k], cols, &bands);
+            for (size_t q = first; q < bands.size(); q++)
+                bs_items.push_back(PlanarBoxItem{crops->left[k], cols, bands[q].row0, bands[q].row1 - bands[q].row0,
+                                                 first, (int)bands.size() - first,
+                                                 (crops->bottom[k] - crops->top[k]) * cols, 0});
+        }
+        bs_o1 = al(sizeof(PlanarBoxItem) * bs_items.size());
+        bs_o2 = bs_o1 + al(sizeof(double) * 4 * bs_items.size());
+        if (!ensure_device(&c->d_boxstat, &c->boxstat_bytes, bs_o2 + sizeof(double) * 3 * bs_items.size()) ||
+            !grow_pinned(&c->h_boxstat, &c->h_boxstat_bytes,
+                         std::max(sizeof(PlanarBoxItem), sizeof(double) * 7) * bs_items.size()))
+            return nullptr;
     }
     uint8_t* dr = (uint8_t*)c->d_prec;
     int* flags = (int*)(dr + R.flags);
@@ -198,6 +219,21 @@ Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int heigh
         PHD_HIPN(launch_sharpness_src(nullptr, pgm, height, width, ncrops, ca.data(), ca.data() + ncrops,
                                       ca.data() + 2 * ncrops, ca.data() + 3 * ncrops, c->d_k255,
                                       (double*)(dr + R.sharp), st));
+    }
+    if (!bs_items.empty()) {
+        // the two launches of the fp64 box statistics and their one download each,
+        // behind the sharpness crops; the host finishes after the call's last wait
+        uint8_t* db = (uint8_t*)c->d_boxstat;
+        double* hb = (double*)c->h_boxstat;
+        const size_t ni = bs_items.size();
+        memcpy(c->h_boxstat, bs_items.data(), sizeof(PlanarBoxItem) * ni);
+        PHD_HIPN(hipMemcpyAsync(db, c->h_boxstat, sizeof(PlanarBoxItem) * ni, hipMemcpyHostToDevice, st));
+        const int ps = c->prof.begin(kPlanarBoxStats, st);
+        PHD_HIPN(launch_planar_box_stats(P, width, (const PlanarBoxItem*)db, (int)ni, (double*)(db + bs_o1),
+                                         (double*)(db + bs_o2), st));
+        c->prof.end(ps, st);
+        PHD_HIPN(hipMemcpyAsync(hb, db + bs_o1, sizeof(double) * 4 * ni, hipMemcpyDeviceToHost, st));
+        PHD_HIPN(hipMemcpyAsync(hb + 4 * ni, db + bs_o2, sizeof(double) * 3 * ni, hipMemcpyDeviceToHost, st));
     }
     PHD_HIPN(hipEventSynchronize(c->ev[5]));
     const int hf = *(const int*)(h.data() + R.flags);
@@ -262,6 +298,28 @@ Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int heigh
                                      (const double*)(h.data() + R.sharp), &why, bscale);
     if (!out) set_error(why);
     else if (box_pal) (void)box_palette_fill(box_pal, ncrops, (int)dec.parents.size(), (const uint32_t*)c->h_boxpal);
+    if (out && !bs_items.empty() && box_stats_alloc(box_stats, ncrops)) {
+        // the items' partials in item order: B = sum / N as the device formed it,
+        // C = sqrt(sum (x - B)^2 / N), S-bar = sum(s) / N
+        const double* p1 = (const double*)c->h_boxstat;
+        const double* p2 = p1 + 4 * bs_items.size();
+        int box = 0;
+        for (size_t q = 0; q < bs_items.size(); q += bs_items[q].count, box++) {
+            const PlanarBoxItem& it = bs_items[q];
+            double a1[4] = {0.0, 0.0, 0.0, 0.0}, a2[3] = {0.0, 0.0, 0.0};
+            for (int j = it.first; j < it.first + it.count; j++) {
+                for (int ch = 0; ch < 4; ch++) a1[ch] += p1[4 * j + ch];
+                for (int ch = 0; ch < 3; ch++) a2[ch] += p2[3 * j + ch];
+            }
+            const double nn = (double)it.npix;
+            double* sb = &box_stats->stats[box].Br;
+            for (int ch = 0; ch < 3; ch++) {
+                sb[ch] = a1[ch] / nn;
+                sb[3 + ch] = std::sqrt(a2[ch] / nn);
+            }
+            box_stats->average_saturation[box] = a1[3] / nn;
+        }
+    }
     return out;
 }
 

@@ -363,6 +363,7 @@ struct ReportArgs {
     const Crop_Boundaries* const* img_crops;
     uint16_t* const* labels;                                  // per-image label maps (device) or NULL
     phd_box_palette* const* box_pal;                          // per-image box palettes (host structs) or NULL
+    phd_box_stats* const* box_stats;                          // per-image box statistics (host structs) or NULL
 };
 
 // How a call's FFT chain is launched: a row and a column launch per image, or
@@ -416,6 +417,14 @@ struct ReportRun : ReportArgs {
     }
     std::vector<long long> bp_off;
     bool box_palettes();                                      // the last stage: the structs of the reported images
+    // box statistics: image i's boxes are summed (it has a struct and boxes);
+    // where its boxes start in the job's download (-1: none)
+    bool sums_boxes(int i) const {
+        return box_stats && box_stats[i] && img_crops && img_crops[i] && img_crops[i]->N > 0;
+    }
+    std::vector<long long> bs_off;
+    bool box_stat_job();                                      // fft_chain()'s first step, with the sharpness launch
+    bool box_statistics();                                    // after box_palettes(): the reported images' structs
 };
 
 // Validation, tables, FFT selection, layout, buffers, the shared-box array.
@@ -575,6 +584,7 @@ bool ReportRun::fft_chain() {
     if (img_crops && !enqueue_sharpness(c, d_imgs, n, width, splan, (double*)(dw + L.C(n, 0) + L.c_sharp),
                                         (long)(L.c_bytes / 8), sf))
         return false;
+    if (box_stats && !box_stat_job()) return false;
     const uint8_t* const* d_ptrs = (const uint8_t* const*)(dw + L.P_dev(n));
     const long a_stride = (long)(L.a_bytes / 8), c_stride = (long)(L.c_bytes / 8);
     for (int g0 = 0; g0 < n; g0 += Q) {
@@ -628,6 +638,22 @@ bool ReportRun::fft_chain() {
     PHD_HIP(hipEventRecord(c->ev_fft, sf));
     t_enq = Clock::now();
     return true;
+}
+
+// The box statistics of every image of the run that has a struct and boxes: one
+// job (one table copy, one memset, k_box_stats and its finish, one download) on
+// the FFT stream ahead of the FFTs, beside the sharpness launch.  It needs only
+// the image bytes and the boxes, so no decision is waited for; its download is
+// on the host by the run's final wait (ev[4] follows the FFT stream).
+bool ReportRun::box_stat_job() {
+    BoxStatJob job;
+    bs_off.assign(n, -1);
+    for (int i = 0; i < n; i++) {
+        if (!sums_boxes(i)) continue;
+        bs_off[i] = (long long)job.recs.size();
+        job.add_image(d_imgs[i], width, img_crops[i]);
+    }
+    return enqueue_box_stat_job(c, job, st);
 }
 
 // The host's palette decisions while the FFTs run, then the palette's second
@@ -908,15 +934,29 @@ bool ReportRun::box_palettes() {
     return true;
 }
 
+// The box statistics structs of the reported images, from the 64 bytes per box
+// box_stat_job's download left in Context::h_boxstat (timings() has waited for
+// it).  A failed image and an image without boxes keep {0, NULL, NULL}.
+bool ReportRun::box_statistics() {
+    if (!box_stats) return true;
+    for (int i = 0; i < n; i++) {
+        if (!out[i] || !sums_boxes(i) || bs_off.empty() || bs_off[i] < 0) continue;
+        if (!box_stats_fill(box_stats[i], img_crops[i], box_stats_host(c) + (size_t)bs_off[i] * kBoxStatOut))
+            return false;
+    }
+    return true;
+}
+
 }  // namespace
 
 bool run_reports(Context* c, const uint8_t* const* d_imgs, int n, int height, int width,
                  const phd_config& cfg, const Crop_Boundaries* crops, Full_Report_Data** out, int* status,
                  hipStream_t stream, const Crop_Boundaries* const* img_crops, uint16_t* const* labels,
-                 phd_box_palette* const* box_pal) {
-    ReportRun r(ReportArgs{c, d_imgs, n, height, width, cfg, crops, out, status, stream, img_crops, labels, box_pal});
+                 phd_box_palette* const* box_pal, phd_box_stats* const* box_stats) {
+    ReportRun r(ReportArgs{c, d_imgs, n, height, width, cfg, crops, out, status, stream, img_crops, labels, box_pal,
+                           box_stats});
     return r.plan() && r.k1() && r.fft_chain() && r.palette_tail() && r.downloads() && r.assemble_groups() &&
-           r.timings() && r.box_palettes() && r.failures == 0;
+           r.timings() && r.box_palettes() && r.box_statistics() && r.failures == 0;
 }
 
 bool run_palette_trace(Context* c, const uint8_t* d_img, int height, int width, const phd_config& cfg,

@@ -20,7 +20,10 @@
 //     (src/color_quantization.c:414-450, 510-576) after the host decisions;
 //   * the palette label map (the parents' pixel lists after
 //     group_irregular_pixels, src/color_quantization.c:342-479) from the same
-//     groups and keep rules (k_planar_labels).
+//     groups and keep rules (k_planar_labels);
+//   * the box statistics: get_rgb_statistics and get_hsv_average
+//     (src/image_processing.c:543-553, 533-540) on crop_image's boxes
+//     (src/image_processing.c:244-266), per band of rows (k_planar_box_stats).
 #include "phd_device.h"
 
 namespace phd {
@@ -443,6 +446,56 @@ __global__ __launch_bounds__(kPlabThreads, kPlabMinWaves) void k_planar_labels(
     }
 }
 
+// The fp64 box statistics (get_rgb_statistics, src/image_processing.c:543-553, and
+// get_hsv_average over rgb2hsv's s, :533-540, on crop_image's box, :244-266):
+// one block per item (a band of whole rows of a box).  kVar == false: the item's
+// fixed-order block sums of r, g, b and s into part[4 * item + c].  kVar ==
+// true: the box's means B = sum / N from its items' sums in item order
+// (sums[4 * k + c], k = first .. first + count - 1), then get_variance's second
+// pass, sum (x - B)^2 per channel into part[3 * item + c].  Plain and untuned:
+// a division per pixel for its row, one pixel per thread and step.
+template <bool kVar>
+__global__ __launch_bounds__(kPT) void k_planar_box_stats(PlanarSrc P, int width,
+                                                          const PlanarBoxItem* __restrict__ items,
+                                                          const double* __restrict__ sums, double* __restrict__ part) {
+    __shared__ double red[kPT / 64];
+    __shared__ double mean[3];
+    const PlanarBoxItem it = items[blockIdx.x];
+    if (kVar) {
+        if (threadIdx.x < 3) {
+            double a = 0.0;
+            for (int k = it.first; k < it.first + it.count; k++) a += sums[4 * k + threadIdx.x];
+            mean[threadIdx.x] = a / (double)it.npix;
+        }
+        __syncthreads();
+    }
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    const int n = it.rows * it.cols;                        // <= kBoxBandElems, or one row's
+    for (int e = threadIdx.x; e < n; e += kPT) {
+        const int row = e / it.cols, x = e - row * it.cols;
+        const long p = (long)(it.row0 + row) * width + it.left + x;
+        const double r = P.r[p], g = P.g[p], b = P.b[p];
+        if (kVar) {
+            const double dr = r - mean[0], dg = g - mean[1], db = b - mean[2];
+            s[0] += dr * dr;
+            s[1] += dg * dg;
+            s[2] += db * db;
+        } else {
+            double h, sat, v;
+            rgb2hsv(r, g, b, h, sat, v);
+            s[0] += r;
+            s[1] += g;
+            s[2] += b;
+            s[3] += sat;
+        }
+    }
+    constexpr int nc = kVar ? 3 : 4;
+    for (int c = 0; c < nc; c++) {
+        const double t = block_sum(s[c], red);
+        if (threadIdx.x == 0) part[nc * blockIdx.x + c] = t;
+    }
+}
+
 unsigned grid_for(long n) { return (unsigned)std::max<long>(1, std::min<long>(kPlanarBlocks, (n + kPT - 1) / kPT)); }
 
 }  // namespace
@@ -528,6 +581,16 @@ hipError_t launch_planar_labels(const PlanarSrc& P, int height, int width, int d
     else
         phd_launch(k_planar_labels<false>, dim3(grid), dim3(kPlabThreads), lds, st, P, npix, width, ds, nw, gp, rules,
                    map);
+    return hipGetLastError();
+}
+
+hipError_t launch_planar_box_stats(const PlanarSrc& P, int width, const PlanarBoxItem* d_items, int nitems,
+                                   double* part1, double* part2, hipStream_t st) {
+    if (nitems <= 0) return hipSuccess;
+    phd_launch(k_planar_box_stats<false>, dim3((unsigned)nitems), dim3(kPT), 0, st, P, width, d_items,
+               (const double*)nullptr, part1);
+    phd_launch(k_planar_box_stats<true>, dim3((unsigned)nitems), dim3(kPT), 0, st, P, width, d_items,
+               (const double*)part1, part2);
     return hipGetLastError();
 }
 

@@ -35,6 +35,7 @@
 #include <cstdlib>
 
 #include "phd_device.h"
+#include "stat_unit.h"
 
 namespace phd {
 
@@ -44,53 +45,9 @@ constexpr int kStThreads = 512;              // 8 waves; kChunk pixels per work 
 constexpr int kStGroups = kChunk / (4 * kStThreads);
 static_assert(kStGroups == 8, "stats tile");
 
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 typedef const __attribute__((address_space(1))) unsigned gu32s;
 
-__device__ __forceinline__ u16x2 as_u16x2(unsigned x) { return __builtin_bit_cast(u16x2, x); }
-
-struct StatAcc {
-    unsigned sr, sg, sb, qr, qg, qb;         // per-thread moments of the run (u32: <= 1024 items)
-    double s64;                              // the partial final group's s (fp64)
-    u16x2 n1;                                // pixels with min == 0 < max (<= 8 per item per half)
-};
-
-// 4 pixels (3 little-endian words w0..w2 = r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3):
-// moments, d added to bucket max of this lane's LDS histogram copy `hk`, the
-// 0.999999 count
-__device__ __forceinline__ void stat4(unsigned w0, unsigned w1, unsigned w2, StatAcc& a, unsigned* hk) {
-    const u16x2 one = {1, 1};
-    const u16x2 r02 = as_u16x2(__builtin_amdgcn_perm(w1, w0, 0x0c060c00u));
-    const u16x2 r13 = as_u16x2(__builtin_amdgcn_perm(w2, w0, 0x0c050c03u));
-    const u16x2 g02 = as_u16x2(__builtin_amdgcn_perm(w1, w0, 0x0c070c01u));
-    const u16x2 g13 = as_u16x2(__builtin_amdgcn_perm(w2, w1, 0x0c060c00u));
-    const u16x2 b02 = as_u16x2(__builtin_amdgcn_perm(w2, w0, 0x0c040c02u));
-    const u16x2 b13 = as_u16x2(__builtin_amdgcn_perm(w2, w1, 0x0c070c01u));
-    a.sr = __builtin_amdgcn_udot2(r02, one, a.sr, false);
-    a.sr = __builtin_amdgcn_udot2(r13, one, a.sr, false);
-    a.sg = __builtin_amdgcn_udot2(g02, one, a.sg, false);
-    a.sg = __builtin_amdgcn_udot2(g13, one, a.sg, false);
-    a.sb = __builtin_amdgcn_udot2(b02, one, a.sb, false);
-    a.sb = __builtin_amdgcn_udot2(b13, one, a.sb, false);
-    a.qr = __builtin_amdgcn_udot2(r02, r02, a.qr, false);
-    a.qr = __builtin_amdgcn_udot2(r13, r13, a.qr, false);
-    a.qg = __builtin_amdgcn_udot2(g02, g02, a.qg, false);
-    a.qg = __builtin_amdgcn_udot2(g13, g13, a.qg, false);
-    a.qb = __builtin_amdgcn_udot2(b02, b02, a.qb, false);
-    a.qb = __builtin_amdgcn_udot2(b13, b13, a.qb, false);
-    const u16x2 m02 = __builtin_elementwise_max(__builtin_elementwise_max(r02, g02), b02);
-    const u16x2 m13 = __builtin_elementwise_max(__builtin_elementwise_max(r13, g13), b13);
-    const u16x2 n02 = __builtin_elementwise_min(__builtin_elementwise_min(r02, g02), b02);
-    const u16x2 n13 = __builtin_elementwise_min(__builtin_elementwise_min(r13, g13), b13);
-    const u16x2 d02 = m02 - n02, d13 = m13 - n13;
-    atomicAdd(&hk[m02.x], (unsigned)d02.x);
-    atomicAdd(&hk[m13.x], (unsigned)d13.x);
-    atomicAdd(&hk[m02.y], (unsigned)d02.y);
-    atomicAdd(&hk[m13.y], (unsigned)d13.y);
-    const u16x2 zero = {0, 0};
-    a.n1 += (u16x2)((n02 == zero) & (m02 != zero)) & one;
-    a.n1 += (u16x2)((n13 == zero) & (m13 != zero)) & one;
-}
+// (StatAcc and stat4, the 4-pixel unit: stat_unit.h, shared with box_stats.hip)
 
 // One launch over a batch of same-size, 4-byte-aligned images.  Work items
 // are (image, chunk of kChunk pixels); each persistent block takes one

@@ -4,7 +4,8 @@ import ctypes
 import os
 
 from .structures import (Blur_Profile, Blur_Vector, Crop_Boundaries, Full_Report_Data, Image_PGM, Image_RGB,
-                         PhdBoxPalette, PhdConfig, PhdImageView, PhdTypedView, PhdYuvView, RGB_Statistics)
+                         PhdBoxPalette, PhdBoxStats, PhdConfig, PhdImageView, PhdTypedView, PhdYuvView,
+                         RGB_Statistics)
 
 def _preload_torch_hip_runtime():
     """One HIP runtime per process.  PyTorch-ROCm ships its own libamdhip64.so
@@ -116,6 +117,8 @@ DECODE_VIEWS_KERNEL = 8    # the typed views' decode to double planes (bit 8: "d
 YUV_VIEWS_KERNEL = 9       # the YCbCr views' conversion to RGB8 (bit 9: "yuv_views")
 PALETTE_LABELS_KERNEL = 10  # the palette label maps (bit 10: "palette_labels")
 BOX_PALETTES_KERNEL = 11   # the box palettes' counting kernel (bit 11: "box_palettes")
+BOX_STATS_KERNEL = 12      # the box statistics' summing kernel (bit 12: "box_stats")
+PLANAR_BOX_STATS_KERNEL = 13  # ... of the fp64 route (bit 13: "planar_box_stats")
 LABEL_NONE = 0xFFFF        # PHD_LABEL_NONE: a pixel in no palette slot's list (-1 as int16)
 lib.phd_debug_time_kernel.restype = ctypes.c_int
 lib.phd_debug_time_kernel.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, P(PhdConfig),
@@ -223,6 +226,31 @@ for _name, _res, _args in (("phd_shutdown", None, []),
                            ("phd_debug_box_counts_host", ctypes.c_int,
                             [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, P(Crop_Boundaries),
                              ctypes.c_void_p]),
+                           # box statistics: per crop box of an image, RGB statistics and average saturation
+                           ("phd_box_stats_device", ctypes.c_int,
+                            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                             P(P(Crop_Boundaries)), P(PhdBoxStats), ctypes.c_void_p]),
+                           ("phd_free_box_stats", None, [P(PhdBoxStats), ctypes.c_int]),
+                           # the four _box_palettes entries plus `box_stats` (n PhdBoxStats) after `box_palettes`
+                           ("phd_report_batch_device_mixed_box_stats", ctypes.c_int,
+                            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, P(PhdConfig),
+                             P(P(Crop_Boundaries)), ctypes.c_void_p, P(PhdBoxPalette), P(PhdBoxStats),
+                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+                           ("phd_report_batch_device_views_box_stats", ctypes.c_int,
+                            [P(PhdImageView), ctypes.c_int, P(PhdConfig), P(P(Crop_Boundaries)), ctypes.c_void_p,
+                             P(PhdBoxPalette), P(PhdBoxStats), P(P(Full_Report_Data)), P(ctypes.c_int),
+                             ctypes.c_void_p]),
+                           ("phd_report_batch_device_typed_views_box_stats", ctypes.c_int,
+                            [P(PhdTypedView), ctypes.c_int, P(PhdConfig), P(P(Crop_Boundaries)), ctypes.c_void_p,
+                             P(PhdBoxPalette), P(PhdBoxStats), P(P(Full_Report_Data)), P(ctypes.c_int),
+                             ctypes.c_void_p]),
+                           ("phd_report_batch_device_yuv_box_stats", ctypes.c_int,
+                            [P(PhdYuvView), ctypes.c_int, P(PhdConfig), P(P(Crop_Boundaries)), ctypes.c_void_p,
+                             P(PhdBoxPalette), P(PhdBoxStats), P(P(Full_Report_Data)), P(ctypes.c_int),
+                             ctypes.c_void_p]),
+                           ("phd_debug_box_stats_host", ctypes.c_int,
+                            [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, P(Crop_Boundaries), ctypes.c_void_p,
+                             ctypes.c_void_p, ctypes.c_void_p]),
                            # which palette kernels a configuration takes (host only)
                            ("phd_debug_palette_path", ctypes.c_int, [P(PhdConfig), ctypes.c_int])):
     try:

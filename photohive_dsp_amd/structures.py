@@ -108,6 +108,13 @@ class PhdBoxPalette(Structure):
     _fields_ = [("n_boxes", c_int), ("n_slots", c_int), ("counts", POINTER(c_uint32))]
 
 
+class PhdBoxStats(Structure):
+    """The box statistics of one image (include/photohive_dsp.h: phd_box_stats): n_boxes
+    RGB_Statistics and n_boxes average saturations in one block, owned by the library until
+    phd_free_box_stats."""
+    _fields_ = [("n_boxes", c_int), ("stats", POINTER(RGB_Statistics)), ("average_saturation", POINTER(c_double))]
+
+
 # phd_yuv_view.matrix, .range and .chroma
 PHD_YUV_BT601, PHD_YUV_BT709 = range(2)
 PHD_YUV_FULL, PHD_YUV_LIMITED = range(2)
