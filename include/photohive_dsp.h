@@ -680,6 +680,78 @@ int phd_report_batch_device_yuv_box_stats(const phd_yuv_view* views, int n_image
 int phd_debug_box_stats_host(const uint8_t* rgb, int height, int width, const Crop_Boundaries* boxes,
                              RGB_Statistics* stats, double* average_saturation, unsigned long long* sums);
 
+/* ---- window blur ----------------------------------------------------------------
+ * The window blur of an image is, per window, the Blur_Profile and the ten
+ * Blur_Vectors of the reference on that crop of the FULL-RESOLUTION image;
+ * downsample_rate plays no part.  A window of image i is a Crop_Boundaries box
+ * with bottom - top == right - left == T inside the image (rows top <= y <
+ * bottom, columns left <= x < right: crop_image, src/image_processing.c:244-266);
+ * T is the call's `window`, 64 or 128.  Its values:
+ *  1. avg = (Br + Bg + Bb) / 3 of get_rgb_statistics(crop) (src/image_processing.c:
+ *     543-553, src/interface.c:78), from the window's exact integer channel sums:
+ *     ((double)sum / 255.0 / n per channel, added in r g b order) / 3.0, n = T * T;
+ *  2. pgm = rgb2pgm(crop) - avg (src/image_processing.c:505-512,
+ *     src/blur_profile.c:233-238);
+ *  3. the unnormalised r2c 2-D DFT, p = re * re + im * im (src/fft_processing.c:
+ *     18-63), then pgm_normalize_fft (:173-213); fft_max is its maximum;
+ *  4. cartesian_to_polar_conversion(T / 2 + 1, T) and calculate_blur_profile
+ *     (src/blur_profile.c:427-458, 34-126): bins[na][nr], angle_bin_size and
+ *     radius_bin_size;
+ *  5. vectorize_blur_profile (src/blur_profile.c:324-416): 10 vectors.
+ * A window whose every p < 1 (a constant grey, black or white window) has
+ * all-zero bins.  Bin sums are kept as bin_scale(T, T / 2 + 1) fixed point, as
+ * everywhere in the library: a window's values depend on its 3 * T * T bytes and
+ * the grid only and are bit-identical on every run. */
+typedef struct phd_window_blur {
+    int n_windows;                         /* windows[i]->N; 0 when image i has none */
+    int num_angle_bins, num_radius_bins;   /* cfg's */
+    int angle_bin_size, radius_bin_size;   /* Blur_Profile's, for a T x T crop (src/blur_profile.c:56-61) */
+    double* bins;                          /* n_windows x na x nr, angle-major; one malloc; NULL when 0 */
+    Blur_Vector* vectors;                  /* n_windows x 10; same malloc */
+    double* fft_max;                       /* n_windows; same malloc */
+} phd_window_blur;
+/* Frees bins (and with it vectors and fft_max) and zeroes the structs; wb ==
+ * NULL is a no-op. */
+void phd_free_window_blur(phd_window_blur* wb, int n);
+
+/* get_blur_profile and vectorize_blur_profile (src/blur_profile.c:250-293,
+ * 324-416; pgm_fft and pgm_normalize_fft, src/fft_processing.c:18-63, 173-213) on
+ * the T x T windows crop_image cuts (src/image_processing.c:244-266) from
+ * n_images packed RGB8 device images of any sizes from T x T and any base
+ * alignment; no byte outside an image's 3 * H * W is read, and the reference's
+ * 350-px size check does not apply (a stage on crops, as phd_box_stats_device).
+ * windows[i] NULL or N == 0 gives n_windows 0.  Of cfg only the five blur fields
+ * are used (radius_partitions, angle_partitions, fft_streak_thresh,
+ * magnitude_thresh, blur_cutoff_ratio_denom); the whole struct must be valid.
+ * Refused with -1 before any device work, phd_last_error naming image and
+ * window and out left zeroed: a NULL image, a size below T, a window other than
+ * 64 or 128, a box whose sides are not T or that leaves the image,
+ * angle_partitions * radius_partitions > 2880, and a grid the polar table of a
+ * T x (T / 2 + 1) spectrum has no place for (a radius bin size of 0, where the
+ * reference divides by zero, src/utilities.c:43-52, e.g. T = 64 with 46 radius
+ * partitions; an element outside the table, where the reference writes out of
+ * bounds, src/blur_profile.c:97-99, e.g. T = 64 at 40 x 72).
+ * All windows of all images go through one launch, one block per window with
+ * the whole window in LDS (profile slot 14); when their bin sums and maxima
+ * exceed PHD_WINDOW_BLUR_BUDGET bytes the call is cut into chunks of that
+ * size, one launch and one download each.  Per call one table upload (twiddles
+ * and window records).  On `stream` or (NULL) the library's, waited for in both
+ * cases.  out: n_images structs (release with phd_free_window_blur).  0 or -1. */
+#define PHD_WINDOW_BLUR_BUDGET 33554432u   /* 32 MiB, on the device and pinned */
+int phd_blur_windows_device(const uint8_t* const* d_images, const int* heights, const int* widths, int n_images,
+                            const Crop_Boundaries* const* windows, int window, const phd_config* cfg,
+                            phd_window_blur* out, void* stream);
+
+/* Validation hook, host only (no GPU): the window blur kernel's own plan, passes
+ * and index maps (blur_window.h; get_blur_profile, src/blur_profile.c:250-293, on
+ * the windows of src/image_processing.c:244-266) over one packed RGB8 image of
+ * host memory at any alignment, finished as the device call finishes; the log
+ * is the C library's.  bins: windows->N x na x nr, vectors: windows->N x 10,
+ * fft_max: windows->N.  0, or -1 with phd_last_error. */
+int phd_debug_window_blur_host(const uint8_t* rgb, int height, int width, const Crop_Boundaries* windows,
+                               int window, const phd_config* cfg, double* bins, Blur_Vector* vectors,
+                               double* fft_max);
+
 /* Palette intermediates of one device-resident image, for bit-exact checks:
  * hist[TL] (arm_octree quantities), parents[*n_parents] (valid_parents in
  * palette order), kept[*n_parents] (pixels surviving group_irregular_pixels).
@@ -791,7 +863,7 @@ int phd_last_timings(double* ms, int n);
  * 1 fft_rows, 2 fft_cols, 3 palette_cutoffs, 4 palette_sums, 5 sharpness,
  * 6 pack_views, 7 classify_views, 8 decode_views, 9 yuv_views,
  * 10 palette_labels, 11 box_palettes, 12 box_stats, 13 the fp64 route's
- * planar_box_stats).
+ * planar_box_stats, 14 window_blur).
  * phd_profile_kernels resets the counters; phd_profile_read returns the
  * accumulated milliseconds and launch count of one kernel. */
 int phd_profile_kernels(unsigned mask);

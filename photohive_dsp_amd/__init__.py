@@ -1,6 +1,7 @@
 """PhotoHive_DSP for MI355X: drop-in get_report / Report / set_bounding_boxes
 backed by hand-written HIP kernels (PhotoHive_DSP_lib/libreport_data.so)."""
-from .core import (Report, box_palettes_device, box_stats_device, convert_yuv_device,  # noqa: F401
+from .core import (Report, blur_map_device, blur_windows_device, box_palettes_device,  # noqa: F401
+                   box_stats_device, convert_yuv_device, window_grid,
                    decode_views_device, get_report, get_reports, make_typed_views, make_views, make_yuv_views,
                    nv12_planes, pack_views_device, quantize_device, report_device, reports_device_labels,
                    reports_device_mixed, reports_device_typed, reports_device_views, reports_device_yuv,

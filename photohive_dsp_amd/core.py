@@ -21,7 +21,7 @@ from .lib import last_error, lib
 from .structures import (PHD_ELEM_F16, PHD_ELEM_F32, PHD_ELEM_F64, PHD_ELEM_U8, PHD_ELEM_U16, PHD_VIEW_SNAP_U8,
                          PHD_YUV_BT601, PHD_YUV_BT709, PHD_YUV_CHROMA_REPLICATE, PHD_YUV_CHROMA_TRIANGLE,
                          PHD_YUV_FULL, PHD_YUV_LIMITED, Crop_Boundaries, Full_Report_Data, PhdBoxPalette, PhdBoxStats,
-                         PhdConfig, PhdImageView, PhdTypedView, PhdYuvView, Pixel_HSV, RGB_Statistics)
+                         PhdConfig, PhdImageView, PhdTypedView, PhdWindowBlur, PhdYuvView, Pixel_HSV, RGB_Statistics)
 from .utils import hsv_to_rgb, image_pgm_to_pillow, to_rgb8
 
 DEFAULTS = dict(h_partitions=18, s_partitions=2, v_partitions=3, black_thresh=0.1, gray_thresh=0.1,
@@ -948,6 +948,112 @@ def blur_profiles_device(images, stream=None, **kw):
                                  bins.ctypes.data_as(POINTER(ctypes.c_double)), vecs, s) != 0:
         raise RuntimeError(f"blur_profiles_device failed: {last_error()}")
     return bins, [[(vecs[10 * i + k].angle, vecs[10 * i + k].magnitude) for k in range(10)] for i in range(n)]
+
+
+WINDOW_DEFAULTS = dict(radius_partitions=16, angle_partitions=36)
+
+
+def window_grid(height, width, window=128, stride=None):
+    """The row-major list of window x window boxes (top, bottom, left, right) at
+    steps of `stride` (default: window) that lie inside a height x width image,
+    and its shape (gh, gw).  Needs no GPU."""
+    stride = window if stride is None else int(stride)
+    if window <= 0 or stride <= 0:
+        raise ValueError("window and stride must be positive")
+    gh = (height - window) // stride + 1 if height >= window else 0
+    gw = (width - window) // stride + 1 if width >= window else 0
+    boxes = [(y * stride, y * stride + window, x * stride, x * stride + window) for y in range(gh) for x in range(gw)]
+    return boxes, (gh, gw)
+
+
+def window_boundaries(boxes):
+    """A Crop_Boundaries of window boxes: a Crop_Boundaries as is, else a sequence
+    of (top, bottom, left, right) tuples or set_bounding_boxes' dicts."""
+    if isinstance(boxes, Crop_Boundaries):
+        return boxes
+    rows = [(b["top"], b["bottom"], b["left"], b["right"]) if isinstance(b, dict) else tuple(b) for b in boxes]
+    a = np.ascontiguousarray(np.array(rows, dtype=np.int32).reshape(-1, 4).T)
+    n = a.shape[1]
+    cols = [(ctypes.c_int * n).from_buffer_copy(a[k].tobytes()) if n else (ctypes.c_int * 0)() for k in range(4)]
+    return Crop_Boundaries(N=n, top=cols[0], bottom=cols[1], left=cols[2], right=cols[3])
+
+
+def blur_windows_device(images, windows, window=128, stream=None, **kw):
+    """The window blur of packed uint8 [H, W, 3] device tensors of any sizes from
+    window x window (phd_blur_windows_device): per image a tuple (bins [n, na, nr]
+    float64, angles [n, 10] int32, magnitudes [n, 10] float32, fft_max [n]
+    float64) -- the reference's Blur_Profile bins, its ten Blur_Vectors and the
+    spectrum maximum on each window's crop of the full-resolution image.
+    windows: per image None, a Crop_Boundaries or a sequence of (top, bottom, left,
+    right) boxes whose sides are `window` (64 or 128).  kw: the report's
+    parameters; radius_partitions and angle_partitions default to 16 and 36 here
+    (the report's 40 x 72 leaves most bins of a small spectrum empty and has no
+    table at 64).  One launch takes every window of every image."""
+    import torch
+    if isinstance(images, torch.Tensor) and images.dim() == 4:
+        images = list(images.unbind(0))
+    images = list(images)
+    for im in images:
+        if not isinstance(im, torch.Tensor) or im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 \
+                or not im.is_contiguous() or im.numel() == 0:
+            raise ValueError("expected contiguous, non-empty uint8 [H, W, 3] device tensors")
+    n = len(images)
+    entries = list(windows) if windows is not None else [None] * n
+    if len(entries) != n:
+        raise ValueError(f"windows has {len(entries)} entries for {n} images")
+    cfg = make_config(**{**WINDOW_DEFAULTS, **kw})
+    if n == 0:
+        return []
+    keep = [None if e is None else window_boundaries(e) for e in entries]
+    arr = (POINTER(Crop_Boundaries) * n)()
+    for i, cb in enumerate(keep):
+        if cb is not None:
+            arr[i] = ctypes.pointer(cb)
+    ptrs = (ctypes.c_void_p * n)(*[im.data_ptr() for im in images])
+    hs = (ctypes.c_int * n)(*[int(im.shape[0]) for im in images])
+    ws = (ctypes.c_int * n)(*[int(im.shape[1]) for im in images])
+    wb = (PhdWindowBlur * n)()
+    if lib.phd_blur_windows_device(ptrs, hs, ws, n, arr, int(window), ctypes.byref(cfg), wb,
+                                   _stream_handle(stream)) != 0:
+        raise RuntimeError(f"blur_windows_device failed: {last_error()}")
+    return _take_window_blur(wb, n, cfg.angle_partitions, cfg.radius_partitions)
+
+
+def _take_window_blur(wb, n, na, nr):
+    """The numpy copies of n filled phd_window_blur structs; the C blocks are freed."""
+    try:
+        out = []
+        for i in range(n):
+            m = int(wb[i].n_windows)
+            bins = np.zeros((m, na, nr), dtype=np.float64)
+            ang = np.zeros((m, 10), dtype=np.int32)
+            mag = np.zeros((m, 10), dtype=np.float32)
+            fmax = np.zeros(m, dtype=np.float64)
+            if m:
+                bins[...] = np.ctypeslib.as_array(wb[i].bins, shape=(m, na, nr))
+                v = np.ctypeslib.as_array(ctypes.cast(wb[i].vectors, POINTER(ctypes.c_int32)), shape=(m, 10, 2))
+                ang[...] = v[..., 0]
+                mag[...] = v[..., 1].copy().view(np.float32)
+                fmax[...] = np.ctypeslib.as_array(wb[i].fft_max, shape=(m,))
+            out.append((bins, ang, mag, fmax))
+        return out
+    finally:
+        lib.phd_free_window_blur(wb, n)
+
+
+def blur_map_device(images, window=128, stride=None, stream=None, **kw):
+    """blur_windows_device over window_grid of every image: per image the same
+    four arrays shaped [gh, gw, ...] (bins [gh, gw, na, nr], angles and
+    magnitudes [gh, gw, 10], fft_max [gh, gw]).  Other inputs -- strided, planar
+    or 4-byte views, YCbCr frames -- go through pack_views_device or
+    convert_yuv_device first."""
+    import torch
+    if isinstance(images, torch.Tensor) and images.dim() == 4:
+        images = list(images.unbind(0))
+    images = list(images)
+    grids = [window_grid(int(im.shape[0]), int(im.shape[1]), window, stride) for im in images]
+    res = blur_windows_device(images, [g[0] for g in grids], window=window, stream=stream, **kw)
+    return [tuple(a.reshape(g[1] + a.shape[1:]) for a in r) for r, g in zip(res, grids)]
 
 
 def set_bounding_boxes(bounding_boxes):

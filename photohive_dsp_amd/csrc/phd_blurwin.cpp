@@ -1,0 +1,248 @@
+// phd_blurwin.cpp -- window blur: per T x T window (T = 64 or 128) of a packed
+// RGB8 image the reference's Blur_Profile and ten Blur_Vectors on that crop:
+// crop_image (src/image_processing.c:244-266), avg of get_rgb_statistics
+// (:543-553, src/interface.c:78), rgb2pgm + remove_dc_bias (:505-512,
+// src/blur_profile.c:233-238), pgm_fft + pgm_normalize_fft
+// (src/fft_processing.c:18-63, 173-213), cartesian_to_polar_conversion +
+// calculate_blur_profile (src/blur_profile.c:427-458, 34-126) and
+// vectorize_blur_profile (:324-416).
+// phd_blur_windows_device (every window of every image of a call in one
+// launch), phd_free_window_blur and the host twin phd_debug_window_blur_host.
+// Plan, box rule and index maps: blur_window.h; kernel: blur_windows.hip.
+
+#include <cstring>
+
+#include "phd_host.h"
+#include "blur_window.h"
+
+using namespace phd;
+
+namespace {
+
+// The polar table of a T x (T/2+1) spectrum on the host, or why the grid has
+// none: build_blur_table's two refusals.  One entry per (T, nr, na) asked for.
+struct HostTable {
+    BlurTable t;
+    std::string why;     // empty: usable
+};
+const HostTable* host_window_table(int T, int nr, int na) {
+    static std::mutex mu;
+    static std::map<std::tuple<int, int, int>, std::unique_ptr<HostTable>> cache;
+    std::lock_guard<std::mutex> lk(mu);
+    auto& e = cache[std::make_tuple(T, nr, na)];
+    if (!e) {
+        e.reset(new HostTable);
+        if (!build_blur_table(T, T, nr, na, &e->t, false)) {
+            e->why = phd_last_error();
+            clear_error();
+        }
+    }
+    return e.get();
+}
+
+// cfg, window and grid: what every entry checks first
+bool window_grid_why(int window, const phd_config* cfg, std::string* why, const HostTable** tab) {
+    if (!cfg) return *why = "NULL cfg", false;
+    if (!win_size_ok(window)) return *why = "window must be 64 or 128, not " + std::to_string(window), false;
+    if (!validate_config(*cfg, why)) return false;
+    const long nbins = (long)cfg->angle_partitions * cfg->radius_partitions;
+    if (nbins > kWinMaxBins)
+        return *why = "angle_partitions * radius_partitions = " + std::to_string(nbins) + " exceeds " +
+                      std::to_string(kWinMaxBins) + " bins",
+               false;
+    *tab = host_window_table(window, cfg->radius_partitions, cfg->angle_partitions);
+    if (!(*tab)->why.empty()) return *why = "window " + std::to_string(window) + ": " + (*tab)->why, false;
+    return true;
+}
+
+bool window_box_why(const Crop_Boundaries* b, int k, int T, int height, int width, std::string* why) {
+    const long long top = b->top[k], bottom = b->bottom[k], left = b->left[k], right = b->right[k];
+    const std::string box = "window " + std::to_string(k) + " (top " + std::to_string(top) + ", bottom " +
+                            std::to_string(bottom) + ", left " + std::to_string(left) + ", right " +
+                            std::to_string(right) + ")";
+    const int rule = win_box_check(b->top[k], b->bottom[k], b->left[k], b->right[k], T, height, width);
+    if (rule == 1) return *why = box + " is not " + std::to_string(T) + " x " + std::to_string(T), false;
+    if (rule == 2)
+        return *why = box + " leaves the " + std::to_string(height) + " x " + std::to_string(width) + " image", false;
+    return true;
+}
+
+bool window_list_why(const Crop_Boundaries* b, int T, int height, int width, std::string* why) {
+    if (!b || b->N == 0) return true;
+    if (b->N < 0 || !b->top || !b->bottom || !b->left || !b->right) return *why = "bad window list", false;
+    for (int k = 0; k < b->N; k++)
+        if (!window_box_why(b, k, T, height, width, why)) return false;
+    return true;
+}
+
+const phd_window_blur kNoWindows = {0, 0, 0, 0, 0, nullptr, nullptr, nullptr};
+
+bool window_blur_alloc(phd_window_blur* wb, int n, const BlurTable& t) {
+    *wb = kNoWindows;
+    wb->num_angle_bins = t.na;
+    wb->num_radius_bins = t.nr;
+    wb->angle_bin_size = t.angle_bin_size;
+    wb->radius_bin_size = t.radius_bin_size;
+    if (n <= 0) return true;
+    const size_t nbins = (size_t)t.na * t.nr;
+    void* p = malloc(sizeof(double) * nbins * n + sizeof(double) * n + sizeof(Blur_Vector) * 10 * (size_t)n);
+    if (!p) {
+        set_error("window blur: out of memory");
+        return false;
+    }
+    wb->n_windows = n;
+    wb->bins = (double*)p;
+    wb->fft_max = wb->bins + nbins * n;
+    wb->vectors = (Blur_Vector*)(wb->fft_max + n);
+    return true;
+}
+
+// Windows of one chunk: their bin sums and maxima fit kWindowBlurBudget bytes
+// (the header's PHD_WINDOW_BLUR_BUDGET, on the device and pinned)
+constexpr size_t kWindowBlurBudget = PHD_WINDOW_BLUR_BUDGET;
+
+}  // namespace
+
+extern "C" void phd_free_window_blur(phd_window_blur* wb, int n) {
+    if (!wb) return;
+    for (int i = 0; i < n; i++) {
+        free(wb[i].bins);
+        wb[i] = kNoWindows;
+    }
+}
+
+extern "C" int phd_blur_windows_device(const uint8_t* const* d_images, const int* heights, const int* widths,
+                                       int n_images, const Crop_Boundaries* const* windows, int window,
+                                       const phd_config* cfg, phd_window_blur* out, void* stream) {
+    clear_error();
+    auto bad = [](const std::string& what) {
+        set_error("phd_blur_windows_device: " + what);
+        return -1;
+    };
+    if (out && n_images > 0)
+        for (int i = 0; i < n_images; i++) out[i] = kNoWindows;
+    if (!d_images || !heights || !widths || !windows || !out || !cfg) return bad("NULL argument");
+    if (n_images <= 0) return bad("n_images must be positive");
+    std::string why;
+    const HostTable* ht = nullptr;
+    if (!window_grid_why(window, cfg, &why, &ht)) return bad(why);
+    const int T = window;
+    std::vector<WinRec> recs;
+    for (int i = 0; i < n_images; i++) {
+        const std::string img = "image " + std::to_string(i) + ": ";
+        if (!d_images[i]) return bad(img + "NULL image");
+        if (heights[i] < T || widths[i] < T)
+            return bad(img + std::to_string(heights[i]) + " x " + std::to_string(widths[i]) +
+                       " is smaller than the window " + std::to_string(T));
+        if (!window_list_why(windows[i], T, heights[i], widths[i], &why)) return bad(img + why);
+        const Crop_Boundaries* b = windows[i];
+        for (int k = 0; b && k < b->N; k++)
+            recs.push_back(WinRec{d_images[i] + 3LL * ((long long)b->top[k] * widths[i] + b->left[k]),
+                                  3LL * widths[i]});
+    }
+    const int na = cfg->angle_partitions, nr = cfg->radius_partitions, nbins = na * nr;
+    if (recs.empty()) {                                      // no window at all: nothing for the device
+        for (int i = 0; i < n_images; i++) window_blur_alloc(&out[i], 0, ht->t);
+        return 0;
+    }
+    if (recs.size() > 0x7FFFFFFFu) return bad("too many windows");
+    for (int i = 0; i < n_images; i++)
+        if (!window_blur_alloc(&out[i], windows[i] ? windows[i]->N : 0, ht->t)) {
+            phd_free_window_blur(out, n_images);
+            return -1;
+        }
+    // window w of the call -> its image's arrays
+    std::vector<std::pair<int, int>> where(recs.size());
+    {
+        size_t w = 0;
+        for (int i = 0; i < n_images; i++)
+            for (int k = 0; k < out[i].n_windows; k++) where[w++] = {i, k};
+    }
+    Context* c = get_context();
+    if (!c) {
+        phd_free_window_blur(out, n_images);
+        return -1;
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    const hipStream_t st = work_stream(c, stream);
+    const size_t nw = recs.size(), per = sizeof(unsigned long long) * nbins + sizeof(double);
+    const size_t chunk = std::min(nw, std::max<size_t>(1, kWindowBlurBudget / per));
+    // device: twiddles | records | chunk bins | chunk maxima; pinned: the table going up, a chunk coming down
+    const size_t o_recs = al(sizeof(double2) * T), up = o_recs + sizeof(WinRec) * nw;
+    const size_t o_bins = al(up), o_fmax = o_bins + al(sizeof(unsigned long long) * nbins * chunk);
+    const size_t total = o_fmax + al(sizeof(double) * chunk), down = o_fmax - o_bins + sizeof(double) * chunk;
+    auto run = [&]() {
+        const BlurTable* tbl = get_table(c, T, T, nr, na);
+        if (!tbl) return false;
+        if (!ensure_device(&c->d_winblur, &c->winblur_bytes, total)) return false;
+        if (!grow_pinned(&c->h_winblur, &c->h_winblur_bytes, std::max(up, down))) return false;
+        uint8_t* h = (uint8_t*)c->h_winblur;
+        uint8_t* d = (uint8_t*)c->d_winblur;
+        memset(h, 0, o_recs);
+        window_twiddles(T, (double2*)h);
+        memcpy(h + o_recs, recs.data(), sizeof(WinRec) * nw);
+        PHD_HIP(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, st));
+        HostPool* pool = host_pool();
+        for (size_t w0 = 0; w0 < nw; w0 += chunk) {
+            const int m = (int)std::min(chunk, nw - w0);
+            const int ps = c->prof.begin(kWindowBlur, st);
+            PHD_HIP(launch_window_blur(T, (const WinRec*)(d + o_recs) + w0, m, (const double2*)d, tbl->d_map, nbins,
+                                       (unsigned long long*)(d + o_bins), (double*)(d + o_fmax), st));
+            c->prof.end(ps, st);
+            // (stream order: the table has gone up before this copy overwrites the pinned block)
+            PHD_HIP(hipMemcpyAsync(h, d + o_bins, down, hipMemcpyDeviceToHost, st));
+            PHD_HIP(hipStreamSynchronize(st));               // the result is on the host: waited for on any stream
+            const unsigned long long* hb = (const unsigned long long*)h;
+            const double* hf = (const double*)(h + (o_fmax - o_bins));
+            auto finish = [&](int j) {
+                const std::pair<int, int> at = where[w0 + j];
+                phd_window_blur& o = out[at.first];
+                o.fft_max[at.second] = hf[j];
+                finish_blur(*tbl, hb + (size_t)j * nbins, hf[j], *cfg, o.bins + (size_t)at.second * nbins,
+                            o.vectors + (size_t)at.second * 10);
+            };
+            if (pool->size() > 0 && m >= 64) pool->parallel_for(m, finish);
+            else
+                for (int j = 0; j < m; j++) finish(j);
+        }
+        c->prof.collect();
+        return true;
+    };
+    if (!run()) {
+        phd_free_window_blur(out, n_images);
+        return -1;
+    }
+    return 0;
+}
+
+// The kernel's steps on the host (blur_windows.hip: window_bins_host), then the
+// device call's own finish.
+extern "C" int phd_debug_window_blur_host(const uint8_t* rgb, int height, int width, const Crop_Boundaries* windows,
+                                          int window, const phd_config* cfg, double* bins, Blur_Vector* vectors,
+                                          double* fft_max) {
+    clear_error();
+    std::string why;
+    const HostTable* ht = nullptr;
+    if (!rgb) why = "NULL image";
+    else if (window_grid_why(window, cfg, &why, &ht)) {
+        if (height < window || width < window)
+            why = std::to_string(height) + " x " + std::to_string(width) + " is smaller than the window " +
+                  std::to_string(window);
+        else if (window_list_why(windows, window, height, width, &why) && windows && windows->N > 0 &&
+                 (!bins || !vectors || !fft_max))
+            why = "NULL bins, vectors or fft_max";
+    }
+    if (!why.empty()) {
+        set_error("phd_debug_window_blur_host: " + why);
+        return -1;
+    }
+    if (!windows || windows->N == 0) return 0;
+    const int nbins = cfg->angle_partitions * cfg->radius_partitions;
+    std::vector<unsigned long long> sums(nbins);
+    for (int k = 0; k < windows->N; k++) {
+        window_bins_host(window, rgb + 3LL * ((long long)windows->top[k] * width + windows->left[k]), 3LL * width,
+                         ht->t.map.data(), nbins, sums.data(), &fft_max[k]);
+        finish_blur(ht->t, sums.data(), fft_max[k], *cfg, bins + (size_t)k * nbins, vectors + (size_t)k * 10);
+    }
+    return 0;
+}

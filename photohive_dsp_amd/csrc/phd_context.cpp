@@ -587,6 +587,11 @@ void destroy_context(Context* c) {
     if (c->h_boxstat) (void)hipHostFree(c->h_boxstat);
     c->h_boxstat = nullptr;
     c->h_boxstat_bytes = 0;
+    dfree(c->d_winblur);
+    c->winblur_bytes = 0;
+    if (c->h_winblur) (void)hipHostFree(c->h_winblur);
+    c->h_winblur = nullptr;
+    c->h_winblur_bytes = 0;
     for (auto& p : c->d_stage2) dfree(p);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     c->h_pin = nullptr;

@@ -135,11 +135,13 @@ bool gfft_run(const GfftPlan& p, const double2* in, double2* out, long count, do
 // ---- per-kernel event timing (opt-in, phd_profile_kernels) -----------------
 enum KernelId {
     kK1 = 0, kFftRows = 1, kFftCols = 2, kCutoffs = 3, kPalSums = 4, kSharp = 5, kPack = 6, kClassify = 7,
-    kDecode = 8, kYuv = 9, kLabels = 10, kBoxPalettes = 11, kBoxStats = 12, kPlanarBoxStats = 13, kNumKernels = 14
+    kDecode = 8, kYuv = 9, kLabels = 10, kBoxPalettes = 11, kBoxStats = 12, kPlanarBoxStats = 13, kWindowBlur = 14,
+    kNumKernels = 15
 };
 static_assert(kBoxPalettes == kProfBoxPalettes, "the box palette launch's profiler slot");
 static_assert(kBoxStats == kProfBoxStats && kPlanarBoxStats == kProfPlanarBoxStats,
               "the box statistics launches' profiler slots");
+static_assert(kWindowBlur == kProfWindowBlur, "the window blur launch's profiler slot");
 static_assert(kClassify == kProfClassify && kDecode == kProfDecode, "the decode launches' profiler slots");
 static_assert(kYuv == kProfYuv, "the YUV conversion launch's profiler slot");
 static_assert(kLabels == kProfLabels, "the label map launch's profiler slot");
@@ -264,6 +266,13 @@ struct Context {
     size_t boxstat_bytes = 0;
     void* h_boxstat = nullptr;
     size_t h_boxstat_bytes = 0;
+    // window blur (phd_blurwin.cpp): twiddles | window records | a chunk's bin
+    // sums | its maxima on the device, and the pinned block the table goes up
+    // from and a chunk's sums and maxima come down to
+    void* d_winblur = nullptr;
+    size_t winblur_bytes = 0;
+    void* h_winblur = nullptr;
+    size_t h_winblur_bytes = 0;
     // the label maps of a run's images that have boxes to count and no map of
     // the caller's: 2 * mh * mw bytes each at 256-byte steps, grow-only
     void* d_labscratch = nullptr;

@@ -303,6 +303,24 @@ hipError_t launch_box_stats(const BoxStatRec* d_recs, const BoxItem* d_items, in
 hipError_t launch_box_stats_finish(const unsigned long long* d_rec, int nboxes, unsigned long long* d_fin,
                                    hipStream_t st);
 
+// ---- window blur (blur_windows.hip; plan and index maps: blur_window.h) -----------
+// Per T x T window (T = 64 or 128) of a packed RGB8 image its polar bin sums
+// (nbins u64 of bin_scale(T, T/2+1) fixed point at d_bins + w * nbins) and its
+// spectrum maximum (d_fmax[w]): n windows, one block each, one launch.  d_tw: T
+// twiddles (window_twiddles); d_binmap: the T x (T/2+1) spectrum's bin table.
+constexpr int kProfWindowBlur = 14;
+struct WinRec {
+    const uint8_t* first;      // the window's first byte: image + 3 * (top * W + left)
+    long long pitch;           // 3 * W
+};
+hipError_t launch_window_blur(int T, const WinRec* d_recs, int n, const double2* d_tw, const uint16_t* d_binmap,
+                              int nbins, unsigned long long* d_bins, double* d_fmax, hipStream_t st);
+void window_twiddles(int T, double2* tw);   // tw[e] = exp(-2 pi i e / T), e < T
+// The kernel's steps on the host for one window (host memory; binmap: the
+// table's host map): the same plan, passes and index maps, the C library's log.
+void window_bins_host(int T, const uint8_t* first, long long pitch, const uint16_t* binmap, int nbins,
+                      unsigned long long* bins, double* fmax_out);
+
 // Row pass: luma - avg of two rows as one complex sequence, FFT, split, write
 // the half spectra column-major into inter[wf][height].
 // Runtime-plan FFT passes over a batch of same-size images in one launch each

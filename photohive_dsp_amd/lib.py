@@ -4,7 +4,7 @@ import ctypes
 import os
 
 from .structures import (Blur_Profile, Blur_Vector, Crop_Boundaries, Full_Report_Data, Image_PGM, Image_RGB,
-                         PhdBoxPalette, PhdBoxStats, PhdConfig, PhdImageView, PhdTypedView, PhdYuvView,
+                         PhdBoxPalette, PhdBoxStats, PhdConfig, PhdImageView, PhdTypedView, PhdWindowBlur, PhdYuvView,
                          RGB_Statistics)
 
 def _preload_torch_hip_runtime():
@@ -119,6 +119,7 @@ PALETTE_LABELS_KERNEL = 10  # the palette label maps (bit 10: "palette_labels")
 BOX_PALETTES_KERNEL = 11   # the box palettes' counting kernel (bit 11: "box_palettes")
 BOX_STATS_KERNEL = 12      # the box statistics' summing kernel (bit 12: "box_stats")
 PLANAR_BOX_STATS_KERNEL = 13  # ... of the fp64 route (bit 13: "planar_box_stats")
+WINDOW_BLUR_KERNEL = 14    # the window blur's one-block-per-window kernel (bit 14: "window_blur")
 LABEL_NONE = 0xFFFF        # PHD_LABEL_NONE: a pixel in no palette slot's list (-1 as int16)
 lib.phd_debug_time_kernel.restype = ctypes.c_int
 lib.phd_debug_time_kernel.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, P(PhdConfig),
@@ -251,6 +252,14 @@ for _name, _res, _args in (("phd_shutdown", None, []),
                            ("phd_debug_box_stats_host", ctypes.c_int,
                             [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, P(Crop_Boundaries), ctypes.c_void_p,
                              ctypes.c_void_p, ctypes.c_void_p]),
+                           # window blur: per 64- or 128-px window of an image, blur profile and vectors
+                           ("phd_blur_windows_device", ctypes.c_int,
+                            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                             P(P(Crop_Boundaries)), ctypes.c_int, P(PhdConfig), P(PhdWindowBlur), ctypes.c_void_p]),
+                           ("phd_free_window_blur", None, [P(PhdWindowBlur), ctypes.c_int]),
+                           ("phd_debug_window_blur_host", ctypes.c_int,
+                            [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, P(Crop_Boundaries), ctypes.c_int,
+                             P(PhdConfig), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
                            # which palette kernels a configuration takes (host only)
                            ("phd_debug_palette_path", ctypes.c_int, [P(PhdConfig), ctypes.c_int])):
     try:

@@ -115,6 +115,15 @@ class PhdBoxStats(Structure):
     _fields_ = [("n_boxes", c_int), ("stats", POINTER(RGB_Statistics)), ("average_saturation", POINTER(c_double))]
 
 
+class PhdWindowBlur(Structure):
+    """The window blur of one image (include/photohive_dsp.h: phd_window_blur): n_windows x
+    na x nr bins, n_windows x 10 vectors and n_windows spectrum maxima in one block, owned by
+    the library until phd_free_window_blur."""
+    _fields_ = [("n_windows", c_int), ("num_angle_bins", c_int), ("num_radius_bins", c_int),
+                ("angle_bin_size", c_int), ("radius_bin_size", c_int),
+                ("bins", POINTER(c_double)), ("vectors", POINTER(Blur_Vector)), ("fft_max", POINTER(c_double))]
+
+
 # phd_yuv_view.matrix, .range and .chroma
 PHD_YUV_BT601, PHD_YUV_BT709 = range(2)
 PHD_YUV_FULL, PHD_YUV_LIMITED = range(2)
