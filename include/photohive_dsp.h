@@ -752,6 +752,73 @@ int phd_debug_window_blur_host(const uint8_t* rgb, int height, int width, const 
                                int window, const phd_config* cfg, double* bins, Blur_Vector* vectors,
                                double* fft_max);
 
+/* ---- blur vectors: the window blur finished on the device ------------------------
+ * Per window the ten Blur_Vectors and fft_max of the window blur above, left in
+ * device memory; the bins are never formed outside the window's block.  After
+ * the kernel's binning the same block runs the finish (blur_window.h):
+ *  - G_s = 1 / (2 * log(sqrt(fft_max) + 1)) (pgm_normalize_fft,
+ *    src/fft_processing.c:192) and, per bin, (double)sum / bin_scale * G_s / count
+ *    (calculate_blur_profile's averaging, src/blur_profile.c:106-116; 0 for an
+ *    empty bin or a zero sum), one thread per bin;
+ *  - vectorize_blur_profile (src/blur_profile.c:324-416): the per-angle totals over
+ *    the first nr / blur_cutoff_ratio_denom radii and their average (:341-349),
+ *    convolve_1d with the 5-tap box and / 5 (src/filtering.c:12-24), the three
+ *    local-maximum rules in increasing angle with at most ten maxima (:358-379),
+ *    and per maximum the perpendicular angle, the blur_avg > avg rejection, the
+ *    first radius below magnitude_thresh, magnitude = (float)r / (float)nr and
+ *    angle = (int)(180 * ((float)a / (float)na) - 90) (:384-414); entries past the
+ *    last maximum are zero (calloc, :297-302).  Every fp64 sum runs in the
+ *    reference's order.
+ * fft_max is bit-identical to phd_blur_windows_device's (the same code).  The
+ * vectors are the reference's on that crop; they equal phd_blur_windows_device's
+ * unless a bin lies within the last-place difference of the two logs (the device
+ * library's fp64 log here, the C library's on the host there) of
+ * magnitude_thresh or of another comparison the rules make.  A window's values
+ * depend on its 3 * T * T bytes and the grid only: bit-identical on every run and
+ * wherever the window sits in the call.
+ *
+ * d_vectors[i]: device pointer, 4-byte aligned, receives n_i x 10 Blur_Vectors;
+ * d_fft_max[i]: device pointer, 8-byte aligned, receives n_i doubles (d_fft_max ==
+ * NULL or d_fft_max[i] == NULL: no maxima for that image).  n_i is windows[i]->N
+ * or gh * gw; d_vectors[i] may be NULL only when n_i == 0.  Nothing is written
+ * outside those 80 * n_i and 8 * n_i bytes.  Images as for
+ * phd_blur_windows_device: packed RGB8 device images of any sizes from T x T at
+ * any base alignment, no byte outside an image's 3 * H * W read.
+ * Refused with -1 before any device work, phd_last_error naming image and window:
+ * everything phd_blur_windows_device refuses, a non-positive stride, a NULL
+ * d_vectors entry of an image that has windows, and angle_partitions < 2
+ * (vectorize_blur_profile reads smooth[1] and smooth[num_angle_bins - 2], which
+ * lie outside the array at one angle bin, src/blur_profile.c:360-374).
+ * One launch (profile slot 15) takes every window of every image; the result is
+ * 88 bytes per window, so there are no chunks and PHD_WINDOW_BLUR_BUDGET plays no
+ * part.  Per call one table upload (twiddles, the bins' element counts, window
+ * records and destinations).  Enqueued on `stream` and not waited for, or (NULL)
+ * on the library's stream and waited for, as phd_pack_views_device.  A call with
+ * no window at all does no device work.  0 or -1. */
+/* Window lists, as phd_blur_windows_device takes them. */
+int phd_blur_vectors_device(const uint8_t* const* d_images, const int* heights, const int* widths, int n_images,
+                            const Crop_Boundaries* const* windows, int window, const phd_config* cfg,
+                            Blur_Vector* const* d_vectors, double* const* d_fft_max, void* stream);
+/* A regular grid per image: window_grid's rule, gh = (H - T) / stride + 1, gw = (W - T) / stride + 1,
+ * row-major; stride > 0, may be smaller (overlap) or larger than the window. */
+int phd_blur_vector_maps_device(const uint8_t* const* d_images, const int* heights, const int* widths, int n_images,
+                                int window, int stride, const phd_config* cfg,
+                                Blur_Vector* const* d_vectors, double* const* d_fft_max, void* stream);
+
+/* Validation hook, host only (no GPU): the blur vector kernel's twin, the window
+ * blur kernel's steps on the host (as phd_debug_window_blur_host) and then the
+ * shared finish (blur_window.h; vectorize_blur_profile, src/blur_profile.c:
+ * 324-416) with the C library's log.  vectors: windows->N x 10, fft_max:
+ * windows->N.  0, or -1 with phd_last_error. */
+int phd_debug_window_vectors_host(const uint8_t* rgb, int height, int width, const Crop_Boundaries* windows,
+                                  int window, const phd_config* cfg, Blur_Vector* vectors, double* fft_max);
+/* Validation hook, host only (no GPU): the shared finish alone over caller-given
+ * bin sums of one window (nbins u64, bin_scale(T, T / 2 + 1) fixed point; fft_max
+ * as pgm_normalize_fft's maximum, src/fft_processing.c:173-213): bins (na x nr, or
+ * NULL) and 10 vectors.  0, or -1 with phd_last_error. */
+int phd_debug_window_finish_host(const unsigned long long* bin_sums, double fft_max, int window,
+                                 const phd_config* cfg, double* bins, Blur_Vector* vectors);
+
 /* Palette intermediates of one device-resident image, for bit-exact checks:
  * hist[TL] (arm_octree quantities), parents[*n_parents] (valid_parents in
  * palette order), kept[*n_parents] (pixels surviving group_irregular_pixels).
@@ -863,7 +930,7 @@ int phd_last_timings(double* ms, int n);
  * 1 fft_rows, 2 fft_cols, 3 palette_cutoffs, 4 palette_sums, 5 sharpness,
  * 6 pack_views, 7 classify_views, 8 decode_views, 9 yuv_views,
  * 10 palette_labels, 11 box_palettes, 12 box_stats, 13 the fp64 route's
- * planar_box_stats, 14 window_blur).
+ * planar_box_stats, 14 window_blur, 15 window_vectors).
  * phd_profile_kernels resets the counters; phd_profile_read returns the
  * accumulated milliseconds and launch count of one kernel. */
 int phd_profile_kernels(unsigned mask);

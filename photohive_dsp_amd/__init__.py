@@ -1,6 +1,7 @@
 """PhotoHive_DSP for MI355X: drop-in get_report / Report / set_bounding_boxes
 backed by hand-written HIP kernels (PhotoHive_DSP_lib/libreport_data.so)."""
-from .core import (Report, blur_map_device, blur_windows_device, box_palettes_device,  # noqa: F401
+from .core import (Report, blur_map_device, blur_vector_maps_device, blur_vectors_device,  # noqa: F401
+                   blur_windows_device, box_palettes_device,
                    box_stats_device, convert_yuv_device, window_grid,
                    decode_views_device, get_report, get_reports, make_typed_views, make_views, make_yuv_views,
                    nv12_planes, pack_views_device, quantize_device, report_device, reports_device_labels,

@@ -1056,6 +1056,93 @@ def blur_map_device(images, window=128, stride=None, stream=None, **kw):
     return [tuple(a.reshape(g[1] + a.shape[1:]) for a in r) for r, g in zip(res, grids)]
 
 
+def _window_images(images):
+    import torch
+    if isinstance(images, torch.Tensor) and images.dim() == 4:
+        images = list(images.unbind(0))
+    images = list(images)
+    for im in images:
+        if not isinstance(im, torch.Tensor) or im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 \
+                or not im.is_contiguous() or im.numel() == 0 or not im.is_cuda:
+            raise ValueError("expected contiguous, non-empty uint8 [H, W, 3] device tensors")
+    return images
+
+
+def _blur_vectors_call(images, counts, shapes, stream, call):
+    """The device tensors of a blur vectors call and the call itself: per image
+    (angles, magnitudes, fft_max) shaped shapes[i] + (10,), (10,), ()."""
+    import torch
+    n = len(images)
+    vec = [torch.empty((c, 10, 2), dtype=torch.int32, device=im.device) for im, c in zip(images, counts)]
+    fmax = [torch.empty((c,), dtype=torch.float64, device=im.device) for im, c in zip(images, counts)]
+    if stream is not None:
+        for t in vec + fmax:
+            t.record_stream(stream)
+    ptrs = (ctypes.c_void_p * n)(*[im.data_ptr() for im in images])
+    hs = (ctypes.c_int * n)(*[int(im.shape[0]) for im in images])
+    ws = (ctypes.c_int * n)(*[int(im.shape[1]) for im in images])
+    pv = (ctypes.c_void_p * n)(*[v.data_ptr() if c else None for v, c in zip(vec, counts)])
+    pf = (ctypes.c_void_p * n)(*[f.data_ptr() if c else None for f, c in zip(fmax, counts)])
+    call(ptrs, hs, ws, n, pv, pf, _stream_handle(stream))
+    out = []
+    for v, f, shp in zip(vec, fmax, shapes):
+        v = v.reshape(tuple(shp) + (10, 2))
+        out.append((v[..., 0], v[..., 1].view(torch.float32), f.reshape(tuple(shp))))
+    return out
+
+
+def blur_vectors_device(images, windows, window=128, stream=None, **kw):
+    """The ten Blur_Vectors and the spectrum maximum of every window, finished on
+    the device (phd_blur_vectors_device): per image a tuple of device tensors
+    (angles [n, 10] int32, magnitudes [n, 10] float32, fft_max [n] float64);
+    angles and magnitudes are views of one interleaved [n, 10, 2] int32 tensor.
+    Inputs and kw as blur_windows_device; angle_partitions must be at least 2.
+    Nothing is copied to the host; with stream= the call is enqueued on that
+    stream and the tensors are valid in its order."""
+    images = _window_images(images)
+    n = len(images)
+    entries = list(windows) if windows is not None else [None] * n
+    if len(entries) != n:
+        raise ValueError(f"windows has {len(entries)} entries for {n} images")
+    cfg = make_config(**{**WINDOW_DEFAULTS, **kw})
+    if n == 0:
+        return []
+    keep = [None if e is None else window_boundaries(e) for e in entries]
+    arr = (POINTER(Crop_Boundaries) * n)()
+    for i, cb in enumerate(keep):
+        if cb is not None:
+            arr[i] = ctypes.pointer(cb)
+    counts = [0 if cb is None else int(cb.N) for cb in keep]
+
+    def call(ptrs, hs, ws, n, pv, pf, s):
+        if lib.phd_blur_vectors_device(ptrs, hs, ws, n, arr, int(window), ctypes.byref(cfg), pv, pf, s) != 0:
+            raise RuntimeError(f"blur_vectors_device failed: {last_error()}")
+
+    return _blur_vectors_call(images, counts, [(c,) for c in counts], stream, call)
+
+
+def blur_vector_maps_device(images, window=128, stride=None, stream=None, **kw):
+    """blur_vectors_device over window_grid of every image, the grid formed by the
+    library (phd_blur_vector_maps_device): per image device tensors (angles
+    [gh, gw, 10] int32, magnitudes [gh, gw, 10] float32, fft_max [gh, gw]
+    float64) -- blur_map_device's vectors and maxima without its bins, and
+    without a copy to the host."""
+    images = _window_images(images)
+    n = len(images)
+    stride = window if stride is None else int(stride)
+    cfg = make_config(**{**WINDOW_DEFAULTS, **kw})
+    if n == 0:
+        return []
+    grids = [window_grid(int(im.shape[0]), int(im.shape[1]), window, stride)[1] if stride > 0 and window > 0
+             else (0, 0) for im in images]
+
+    def call(ptrs, hs, ws, n, pv, pf, s):
+        if lib.phd_blur_vector_maps_device(ptrs, hs, ws, n, int(window), stride, ctypes.byref(cfg), pv, pf, s) != 0:
+            raise RuntimeError(f"blur_vector_maps_device failed: {last_error()}")
+
+    return _blur_vectors_call(images, [g[0] * g[1] for g in grids], grids, stream, call)
+
+
 def set_bounding_boxes(bounding_boxes):
     """core.py:489-515."""
     n = len(bounding_boxes)

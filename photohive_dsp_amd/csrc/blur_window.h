@@ -1,4 +1,4 @@
-// blur_window.h -- the window blur's plan, box rule and LDS layout, host + device.
+// blur_window.h -- the window blur's plan, box rule, LDS layout and finish, host + device.
 //
 // A window is a T x T crop (T = 64 or 128) of a packed RGB8 image: a
 // Crop_Boundaries box with bottom - top == right - left == T inside the image
@@ -30,6 +30,8 @@
 // one or two butterflies per thread with a barrier between load and store.
 #pragma once
 
+#include <math.h>
+#include <stddef.h>
 #include <stdint.h>
 
 // The plan's constants and the box rule build with any host compiler
@@ -81,6 +83,78 @@ WIN_HD int win_box_check(int top, int bottom, int left, int right, int T, int he
     if ((long long)bottom - top != T || (long long)right - left != T) return 1;
     if (top < 0 || left < 0 || bottom > height || right > width) return 2;
     return 0;
+}
+
+// ---- the finish: flat bins and vectors ----------------------------------------------
+// From a window's nbins fixed-point bin sums and its spectrum maximum to the
+// reference's bins and ten Blur_Vectors, as rows that the kernel
+// (blur_windows.hip: k_window_vectors) runs one thread per bin, per angle or per
+// maximum with barriers between them and the host twin (phd_blurwin.cpp:
+// window_finish_host) runs in sequence.  Every row is finish_blur's
+// (phd_assemble.cpp) or vectorize_blur's (phd_blur.cpp) expression, operation for
+// operation and sum for sum in the reference's order: plain IEEE fp64 and fp32
+// operations, no fma.  Only the log differs between the two sides (the C library's
+// on the host, the device library's in the kernel).
+struct WinVector {             // Blur_Vector's layout (src/blur_profile.h:52-55)
+    int angle;
+    float magnitude;
+};
+constexpr int kWinVectors = 10;                      // initialize_blur_vector_group(10), src/blur_profile.c:328
+// pgm_normalize_fft's G_s (src/fft_processing.c:192); infinite for fft_max == 0, where every sum is 0
+WIN_HD double win_gs(double fft_max) { return 1 / (2 * log(sqrt(fft_max) + 1)); }
+// bin b of calculate_blur_profile (src/blur_profile.c:106-116) from its fixed-point sum of log p
+WIN_HD double win_flat_bin(unsigned long long sum, double scale, double gs, unsigned count) {
+    const double q = (double)count;
+    const double s = sum == 0ull ? 0.0 : (double)sum / scale * gs;
+    return q != 0 ? s / q : 0;
+}
+// tot[i] of vectorize_blur_profile (src/blur_profile.c:343-346), rc = nr / denom
+WIN_HD double win_angle_total(const double* flat, int nr, int rc, int i) {
+    double t = 0.0;
+    for (int j = 0; j < rc; j++) t += flat[(size_t)i * nr + j];
+    return t;
+}
+// avg (:341-349)
+WIN_HD double win_angle_avg(const double* tot, int na) {
+    double avg = 0;
+    for (int i = 0; i < na; i++) avg += tot[i];
+    return avg / na;
+}
+// convolve_1d with the 5-tap box of ones, then / 5 (src/filtering.c:12-24)
+WIN_HD double win_smooth(const double* tot, int na, int i) {
+    double s = 0.0;
+    for (int j = 0; j < 5; j++) s += tot[((i - j) % na + na) % na] * 1.0;
+    return s / 5;
+}
+// The local maxima above thr = avg * fft_streak_thresh in increasing angle, ten at
+// most (:358-379).  na >= 2: the rules read sm[1] and sm[na - 2].
+WIN_HD int win_maxima(const double* sm, int na, double thr, int* idx) {
+    int m = 0;
+    if (sm[0] > sm[na - 1] && sm[0] > sm[1] && sm[0] > thr) idx[m++] = 0;
+    for (int i = 1; i < na - 1 && m < kWinVectors; i++)
+        if (sm[i] > sm[i - 1] && sm[i] > sm[i + 1] && sm[i] > thr) idx[m++] = i;
+    if (m < kWinVectors && sm[na - 1] > sm[na - 2] && sm[na - 1] > sm[0] && sm[na - 1] > thr) idx[m++] = na - 1;
+    return m;
+}
+// The vector of the maximum at angle bin imax (:384-414)
+WIN_HD WinVector win_vector(const double* flat, int na, int nr, int rc, double avg, double mag, int imax) {
+    WinVector v;
+    v.angle = 0;
+    v.magnitude = 0.0f;
+    const int a = (imax + na / 2) % na;
+    const double* sig = flat + (size_t)a * nr;
+    double bavg = 0;
+    for (int j = 0; j < rc; j++) bavg += sig[j];
+    if (bavg > avg) return v;
+    int rmax = nr;
+    for (int j = 0; j < nr; j++)
+        if (sig[j] < mag) {
+            rmax = j;
+            break;
+        }
+    v.magnitude = ((float)rmax / (float)nr);
+    v.angle = (int)(180 * ((float)a / (float)na) - 90);
+    return v;
 }
 
 #if defined(__HIPCC__)

@@ -7,8 +7,11 @@
 // 18-63), pgm_normalize_fft (:173-213) and calculate_blur_profile's binning
 // (src/blur_profile.c:34-126) -- with the whole window in LDS: one block takes
 // a window from its RGB bytes to its bin sums, nothing in between goes to HBM.
-// Plan, index maps and butterflies: blur_window.h (shared with the host twin
-// window_bins_host below).
+// k_window_vectors goes on in the same block: the bins' normalisation and
+// vectorize_blur_profile (src/blur_profile.c:324-416) out of LDS, ten
+// Blur_Vectors and the maximum per window to device memory.
+// Plan, index maps, butterflies and the finish's rows: blur_window.h (shared
+// with the host twin window_bins_host below and the finish's, phd_blurwin.cpp).
 #include <cmath>
 
 #include "phd_device.h"
@@ -49,27 +52,39 @@ __device__ __forceinline__ void win_pass(double2* buf, const double2* tw, int ti
     __syncthreads();
 }
 
-// One block per window.  recs[w]: the window's first byte and its image's row
-// pitch.  out: per window nbins u64 bin sums (bin_scale(T, T/2+1) fixed point),
-// fmax: per window the largest p.  Plain stores: a window has one owner.
+// A block's LDS, and steps 1 to 5 of a window: from its RGB bytes to its nbins
+// fixed-point bin sums in s.lb and the waves' maxima of p in s.red (as doubles,
+// one per wave), behind a barrier.  Shared by k_window_blur and k_window_vectors.
 template <int T>
-__global__ __launch_bounds__(WinPlan<T>::kThreads) void k_window_blur(const WinRec* __restrict__ recs,
-                                                                      const double2* __restrict__ twg,
-                                                                      const uint16_t* __restrict__ binmap, int nbins,
-                                                                      double bscale,
-                                                                      unsigned long long* __restrict__ out,
-                                                                      double* __restrict__ fmax_out) {
+struct WinLds {
+    double2* buf;                  // win_elems(T): the spectrum
+    double2* tw;                   // T twiddles
+    double2* lt;                   // the log table
+    unsigned long long* red;       // 4 per wave: the channel sums, then the maxima
+    unsigned long long* lb;        // the bins (k / 255.0 until step 3 is done)
+};
+template <int T>
+__device__ __forceinline__ WinLds<T> win_lds(unsigned char* smem) {
+    WinLds<T> s;
+    s.buf = reinterpret_cast<double2*>(smem);
+    s.tw = s.buf + win_elems(T);
+    s.lt = s.tw + T;
+    s.red = reinterpret_cast<unsigned long long*>(s.lt + kLogTab);
+    s.lb = s.red + 4 * (WinPlan<T>::kThreads / 64);
+    return s;
+}
+template <int T>
+__device__ __forceinline__ void win_bin_sums(const WinRec rec, const double2* __restrict__ twg,
+                                             const uint16_t* __restrict__ binmap, int nbins, double bscale,
+                                             const WinLds<T>& s, int tid) {
     using P = WinPlan<T>;
     constexpr int NT = P::kThreads, NW = NT / 64;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    double2* buf = reinterpret_cast<double2*>(smem);
-    double2* tw = buf + win_elems(T);
-    double2* lt = tw + T;
-    unsigned long long* red = reinterpret_cast<unsigned long long*>(lt + kLogTab);
-    unsigned long long* lb = red + 4 * NW;
+    double2* buf = s.buf;
+    double2* tw = s.tw;
+    double2* lt = s.lt;
+    unsigned long long* red = s.red;
+    unsigned long long* lb = s.lb;
     double* k255 = reinterpret_cast<double*>(lb);            // until step 3 is done
-    const int tid = threadIdx.x;
-    const WinRec rec = recs[blockIdx.x];
 
     // 1. the window's rows as 4-pixel units (12 bytes, three words at the unit's
     //    own address: no byte outside the window is read)
@@ -154,6 +169,25 @@ __global__ __launch_bounds__(WinPlan<T>::kThreads) void k_window_blur(const WinR
     double* redd = reinterpret_cast<double*>(red);
     if (lane_id() == 0) redd[tid >> 6] = mx;            // (red's sums were read before the barriers above)
     __syncthreads();
+}
+
+// One block per window.  recs[w]: the window's first byte and its image's row
+// pitch.  out: per window nbins u64 bin sums (bin_scale(T, T/2+1) fixed point),
+// fmax: per window the largest p.  Plain stores: a window has one owner.
+template <int T>
+__global__ __launch_bounds__(WinPlan<T>::kThreads) void k_window_blur(const WinRec* __restrict__ recs,
+                                                                      const double2* __restrict__ twg,
+                                                                      const uint16_t* __restrict__ binmap, int nbins,
+                                                                      double bscale,
+                                                                      unsigned long long* __restrict__ out,
+                                                                      double* __restrict__ fmax_out) {
+    constexpr int NT = WinPlan<T>::kThreads, NW = NT / 64;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const WinLds<T> s = win_lds<T>(smem);
+    const int tid = threadIdx.x;
+    win_bin_sums<T>(recs[blockIdx.x], twg, binmap, nbins, bscale, s, tid);
+    const unsigned long long* lb = s.lb;
+    const double* redd = reinterpret_cast<const double*>(s.red);
 
     // 6. the bins and the maximum, once
     unsigned long long* o = out + (size_t)blockIdx.x * nbins;
@@ -164,6 +198,68 @@ __global__ __launch_bounds__(WinPlan<T>::kThreads) void k_window_blur(const WinR
         for (int q = 0; q < NW; q++) m = fmax(m, redd[q]);
         fmax_out[blockIdx.x] = m;
     }
+}
+
+// k_window_blur's steps 1 to 5, then the finish (blur_window.h) in the same block:
+// the window's ten Blur_Vectors to dst[w].vectors and its spectrum maximum to
+// dst[w].fft_max (or nowhere: NULL).  The bins never leave LDS.  After step 5 the
+// spectrum, the twiddles and the log table are dead: the per-angle totals, the
+// smoothed totals and the maxima live at smem + scr_off (0: over the spectrum;
+// the launcher places them behind the bins where 16 na + 64 bytes do not fit
+// there), and the flat bins replace the u64 sums in place.
+//   6. gs from the maximum (every thread: one fp64 log each, no barrier), one
+//      thread per bin: flat[b];                                        barrier
+//   7. one thread per angle: tot[i];                                   barrier
+//   8. one thread per angle: the smoothed tot[i]; the last thread: avg; barrier
+//   9. the last thread: the ordered scan for maxima;                   barrier
+//  10. one thread per vector: win_vector of its maximum, or zeros.
+template <int T>
+__global__ __launch_bounds__(WinPlan<T>::kThreads) void k_window_vectors(
+    const WinRec* __restrict__ recs, const WinDst* __restrict__ dst, const double2* __restrict__ twg,
+    const uint16_t* __restrict__ binmap, const uint16_t* __restrict__ counts, int nbins, int na, int nr, int rc,
+    double bscale, double streak, double mag, int scr_off) {
+    constexpr int NT = WinPlan<T>::kThreads, NW = NT / 64;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const WinLds<T> s = win_lds<T>(smem);
+    const int tid = threadIdx.x;
+    win_bin_sums<T>(recs[blockIdx.x], twg, binmap, nbins, bscale, s, tid);
+    const WinDst d = dst[blockIdx.x];
+    unsigned long long* lb = s.lb;
+    const double* redd = reinterpret_cast<const double*>(s.red);
+    const double* flat = reinterpret_cast<const double*>(lb);
+    double* tot = reinterpret_cast<double*>(smem + scr_off);
+    double* sm = tot + na;
+    double* avgp = sm + na;                                  // avg, then m and the maxima's angle bins
+    int* mx = reinterpret_cast<int*>(avgp + 1);
+
+    double fm = 0.0;
+#pragma unroll
+    for (int q = 0; q < NW; q++) fm = fmax(fm, redd[q]);
+    const double gs = win_gs(fm);
+    for (int i = tid; i < nbins; i += NT)
+        lb[i] = (unsigned long long)__double_as_longlong(win_flat_bin(lb[i], bscale, gs, counts[i]));
+    __syncthreads();
+    for (int i = tid; i < na; i += NT) tot[i] = win_angle_total(flat, nr, rc, i);
+    __syncthreads();
+    for (int i = tid; i < na; i += NT) sm[i] = win_smooth(tot, na, i);
+    double avg = 0.0;
+    if (tid == NT - 1) avg = win_angle_avg(tot, na);
+    __syncthreads();
+    if (tid == NT - 1) {
+        mx[0] = win_maxima(sm, na, avg * streak, mx + 1);
+        avgp[0] = avg;
+    }
+    __syncthreads();
+    if (tid < kWinVectors) {
+        WinVector v;
+        v.angle = 0;
+        v.magnitude = 0.0f;
+        if (tid < mx[0]) v = win_vector(flat, na, nr, rc, avgp[0], mag, mx[1 + tid]);
+        // (4-byte stores: the vectors are 4-byte aligned)
+        d.vectors[tid].angle = v.angle;
+        d.vectors[tid].magnitude = v.magnitude;
+    }
+    if (tid == 0 && d.fft_max) *d.fft_max = fm;
 }
 
 template <int T>
@@ -179,7 +275,45 @@ hipError_t launch_t(const WinRec* d_recs, int n, const double2* d_tw, const uint
     return hipGetLastError();
 }
 
+// bytes of k_window_vectors' totals, smoothed totals, avg and maxima
+constexpr size_t win_scratch(int na) { return 16 * (size_t)na + 64; }
+
+template <int T>
+hipError_t launch_vectors_t(const WinRec* d_recs, const WinDst* d_dst, int n, const double2* d_tw,
+                            const uint16_t* d_binmap, const uint16_t* d_counts, int na, int nr, int denom,
+                            double streak, double mag, hipStream_t st) {
+    static bool once = ((void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_window_vectors<T>),
+                                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
+                        true);
+    (void)once;
+    const int nbins = na * nr;
+    size_t lds = win_lds_fixed<T>() + win_lds_bins(nbins);
+    // the scratch lies over the dead spectrum, twiddles and log table (everything before the waves'
+    // partials); only T = 64 with more than 2172 angle bins (and so one radius bin) needs bytes of its own
+    constexpr size_t dead = sizeof(double2) * (win_elems(T) + T + kLogTab);
+    static_assert(T == 64 || win_scratch(kWinMaxBins) <= dead, "the scratch of any grid fits a 128-window's spectrum");
+    size_t scr_off = 0;
+    if (win_scratch(na) > dead) {
+        scr_off = lds;
+        lds += win_scratch(na);
+    }
+    if (lds > 163840) return hipErrorInvalidValue;
+    phd_launch(k_window_vectors<T>, dim3(n), dim3(WinPlan<T>::kThreads), lds, st, d_recs, d_dst, d_tw, d_binmap,
+               d_counts, nbins, na, nr, nr / denom, bin_scale(T, T / 2 + 1), streak, mag, (int)scr_off);
+    return hipGetLastError();
+}
+
 }  // namespace
+
+hipError_t launch_window_vectors(int T, const WinRec* d_recs, const WinDst* d_dst, int n, const double2* d_tw,
+                                 const uint16_t* d_binmap, const uint16_t* d_counts, int na, int nr, int denom,
+                                 double streak, double mag, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    if (na < 2 || nr <= 0 || denom <= 0 || (long long)na * nr > kWinMaxBins || !win_size_ok(T))
+        return hipErrorInvalidValue;
+    return T == 64 ? launch_vectors_t<64>(d_recs, d_dst, n, d_tw, d_binmap, d_counts, na, nr, denom, streak, mag, st)
+                   : launch_vectors_t<128>(d_recs, d_dst, n, d_tw, d_binmap, d_counts, na, nr, denom, streak, mag, st);
+}
 
 hipError_t launch_window_blur(int T, const WinRec* d_recs, int n, const double2* d_tw, const uint16_t* d_binmap,
                               int nbins, unsigned long long* d_bins, double* d_fmax, hipStream_t st) {

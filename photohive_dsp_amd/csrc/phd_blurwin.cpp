@@ -8,7 +8,12 @@
 // vectorize_blur_profile (:324-416).
 // phd_blur_windows_device (every window of every image of a call in one
 // launch), phd_free_window_blur and the host twin phd_debug_window_blur_host.
-// Plan, box rule and index maps: blur_window.h; kernel: blur_windows.hip.
+// Blur vectors: phd_blur_vectors_device and phd_blur_vector_maps_device leave
+// each window's ten vectors and its maximum in device memory, finished by the
+// window's own block; their twin phd_debug_window_vectors_host and the finish
+// alone, phd_debug_window_finish_host.
+// Plan, box rule, index maps and the finish's rows: blur_window.h; kernels:
+// blur_windows.hip.
 
 #include <cstring>
 
@@ -212,6 +217,211 @@ extern "C" int phd_blur_windows_device(const uint8_t* const* d_images, const int
         phd_free_window_blur(out, n_images);
         return -1;
     }
+    return 0;
+}
+
+// ---- blur vectors: the finish in the window's own block ---------------------------
+namespace {
+
+static_assert(sizeof(WinVector) == sizeof(Blur_Vector) && offsetof(WinVector, angle) == offsetof(Blur_Vector, angle) &&
+                  offsetof(WinVector, magnitude) == offsetof(Blur_Vector, magnitude),
+              "WinVector is Blur_Vector");
+
+// The rows of the shared finish (blur_window.h) in sequence, one window: what
+// k_window_vectors runs between barriers.  flat: na x nr or nullptr.
+void window_finish_host(const BlurTable& t, const unsigned long long* sums, double fmax, int T, const phd_config& cfg,
+                        double* flat, Blur_Vector* out) {
+    const int na = cfg.angle_partitions, nr = cfg.radius_partitions, rc = nr / cfg.blur_cutoff_ratio_denom;
+    const double scale = bin_scale(T, T / 2 + 1), gs = win_gs(fmax);
+    std::vector<double> own, tot(na), sm(na);
+    if (!flat) {
+        own.resize((size_t)na * nr);
+        flat = own.data();
+    }
+    for (int b = 0; b < na * nr; b++) flat[b] = win_flat_bin(sums[b], scale, gs, (unsigned)t.counts[b]);
+    for (int i = 0; i < na; i++) tot[i] = win_angle_total(flat, nr, rc, i);
+    const double avg = win_angle_avg(tot.data(), na);
+    for (int i = 0; i < na; i++) sm[i] = win_smooth(tot.data(), na, i);
+    int idx[kWinVectors];
+    const int m = win_maxima(sm.data(), na, avg * cfg.fft_streak_thresh, idx);
+    for (int k = 0; k < kWinVectors; k++) {
+        WinVector v = {0, 0.0f};                             // calloc, src/blur_profile.c:297-302
+        if (k < m) v = win_vector(flat, na, nr, rc, avg, cfg.magnitude_thresh, idx[k]);
+        out[k] = Blur_Vector{v.angle, v.magnitude};
+    }
+}
+
+// what the vector entries check on top of window_grid_why
+bool vector_grid_why(int window, const phd_config* cfg, std::string* why, const HostTable** tab) {
+    if (!window_grid_why(window, cfg, why, tab)) return false;
+    if (cfg->angle_partitions < 2)
+        return *why = "angle_partitions must be at least 2 (vectorize_blur_profile reads smooth[1] and "
+                      "smooth[num_angle_bins - 2], src/blur_profile.c:360-374), not " +
+                      std::to_string(cfg->angle_partitions),
+               false;
+    return true;
+}
+
+// Both vector entries: window lists (stride 0) or a regular grid per image (stride > 0).
+int blur_vectors_call(const char* entry, const uint8_t* const* d_images, const int* heights, const int* widths,
+                      int n_images, const Crop_Boundaries* const* windows, int window, int stride,
+                      const phd_config* cfg, Blur_Vector* const* d_vectors, double* const* d_fft_max, void* stream) {
+    clear_error();
+    auto bad = [&](const std::string& what) {
+        set_error(std::string(entry) + ": " + what);
+        return -1;
+    };
+    const bool grid = !windows;
+    if (!d_images || !heights || !widths || !d_vectors || !cfg) return bad("NULL argument");
+    if (n_images <= 0) return bad("n_images must be positive");
+    std::string why;
+    const HostTable* ht = nullptr;
+    if (!vector_grid_why(window, cfg, &why, &ht)) return bad(why);
+    if (grid && stride <= 0) return bad("stride must be positive, not " + std::to_string(stride));
+    const int T = window;
+    // windows of image i: windows[i]->N, or the grid's gh * gw (window_grid's rule)
+    std::vector<long long> count(n_images, 0), gws(n_images, 0);
+    long long nw = 0;
+    for (int i = 0; i < n_images; i++) {
+        const std::string img = "image " + std::to_string(i) + ": ";
+        if (!d_images[i]) return bad(img + "NULL image");
+        if (heights[i] < T || widths[i] < T)
+            return bad(img + std::to_string(heights[i]) + " x " + std::to_string(widths[i]) +
+                       " is smaller than the window " + std::to_string(T));
+        if (grid) {
+            gws[i] = (widths[i] - T) / stride + 1;
+            count[i] = ((long long)(heights[i] - T) / stride + 1) * gws[i];
+        } else {
+            if (!window_list_why(windows[i], T, heights[i], widths[i], &why)) return bad(img + why);
+            count[i] = windows[i] ? windows[i]->N : 0;
+        }
+        if (count[i] > 0 && !d_vectors[i])
+            return bad(img + "NULL d_vectors for " + std::to_string(count[i]) + " windows");
+        nw += count[i];
+    }
+    if (nw == 0) return 0;                                   // no window at all: nothing for the device
+    if (nw > 0x7FFFFFFFLL) return bad("too many windows");
+    const int na = cfg->angle_partitions, nr = cfg->radius_partitions, nbins = na * nr;
+    Context* c = get_context();
+    if (!c) return -1;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const hipStream_t st = work_stream(c, stream);
+    // the call's table: twiddles | the bins' element counts (u16) | window records | their destinations
+    const size_t o_counts = al(sizeof(double2) * T), o_recs = o_counts + al(sizeof(uint16_t) * nbins);
+    const size_t o_dst = o_recs + al(sizeof(WinRec) * (size_t)nw), bytes = o_dst + sizeof(WinDst) * (size_t)nw;
+    auto run = [&]() {
+        const BlurTable* tbl = get_table(c, T, T, nr, na);
+        if (!tbl) return false;
+        // upload_table's rule (phd_inputs.cpp), filled in place: the last launch that read the context's
+        // table may still run on a caller's stream that nobody has drained
+        if (!c->ev_views) PHD_HIP(hipEventCreateWithFlags(&c->ev_views, hipEventDisableTiming));
+        else PHD_HIP(hipEventSynchronize(c->ev_views));
+        if (!ensure_device(&c->d_views, &c->views_bytes, bytes)) return false;
+        if (!grow_pinned(&c->h_views, &c->h_views_bytes, bytes)) return false;
+        uint8_t* h = (uint8_t*)c->h_views;
+        uint8_t* d = (uint8_t*)c->d_views;
+        memset(h, 0, o_recs);
+        window_twiddles(T, (double2*)h);
+        uint16_t* hc = (uint16_t*)(h + o_counts);
+        for (int b = 0; b < nbins; b++) hc[b] = (uint16_t)tbl->counts[b];
+        WinRec* recs = (WinRec*)(h + o_recs);
+        WinDst* dst = (WinDst*)(h + o_dst);
+        memset(h + o_recs + sizeof(WinRec) * (size_t)nw, 0, o_dst - o_recs - sizeof(WinRec) * (size_t)nw);
+        size_t w = 0;
+        for (int i = 0; i < n_images; i++) {
+            const long long pitch = 3LL * widths[i];
+            for (long long k = 0; k < count[i]; k++, w++) {
+                const long long top = grid ? (k / gws[i]) * stride : windows[i]->top[k];
+                const long long left = grid ? (k % gws[i]) * stride : windows[i]->left[k];
+                recs[w] = WinRec{d_images[i] + top * pitch + 3 * left, pitch};
+                dst[w] = WinDst{(WinVector*)d_vectors[i] + kWinVectors * k,
+                                d_fft_max && d_fft_max[i] ? d_fft_max[i] + k : nullptr};
+            }
+        }
+        PHD_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st));
+        const int ps = c->prof.begin(kWindowVectors, st);
+        const hipError_t e = launch_window_vectors(T, (const WinRec*)(d + o_recs), (const WinDst*)(d + o_dst), (int)nw,
+                                                   (const double2*)d, tbl->d_map, (const uint16_t*)(d + o_counts), na,
+                                                   nr, cfg->blur_cutoff_ratio_denom, cfg->fft_streak_thresh,
+                                                   cfg->magnitude_thresh, st);
+        c->prof.end(ps, st);
+        PHD_HIP(e);
+        if (!table_launched(c, st)) return false;
+        if (!stream) {                                       // the library's stream: waited for
+            PHD_HIP(hipStreamSynchronize(st));
+            c->prof.collect();
+        }
+        return true;
+    };
+    return run() ? 0 : -1;
+}
+
+}  // namespace
+
+extern "C" int phd_blur_vectors_device(const uint8_t* const* d_images, const int* heights, const int* widths,
+                                       int n_images, const Crop_Boundaries* const* windows, int window,
+                                       const phd_config* cfg, Blur_Vector* const* d_vectors,
+                                       double* const* d_fft_max, void* stream) {
+    if (!windows) {
+        clear_error();
+        set_error("phd_blur_vectors_device: NULL argument");
+        return -1;
+    }
+    return blur_vectors_call("phd_blur_vectors_device", d_images, heights, widths, n_images, windows, window, 0, cfg,
+                             d_vectors, d_fft_max, stream);
+}
+
+extern "C" int phd_blur_vector_maps_device(const uint8_t* const* d_images, const int* heights, const int* widths,
+                                           int n_images, int window, int stride, const phd_config* cfg,
+                                           Blur_Vector* const* d_vectors, double* const* d_fft_max, void* stream) {
+    return blur_vectors_call("phd_blur_vector_maps_device", d_images, heights, widths, n_images, nullptr, window,
+                             stride, cfg, d_vectors, d_fft_max, stream);
+}
+
+// k_window_vectors' twin: window_bins_host, then the shared finish.
+extern "C" int phd_debug_window_vectors_host(const uint8_t* rgb, int height, int width,
+                                             const Crop_Boundaries* windows, int window, const phd_config* cfg,
+                                             Blur_Vector* vectors, double* fft_max) {
+    clear_error();
+    std::string why;
+    const HostTable* ht = nullptr;
+    if (!rgb) why = "NULL image";
+    else if (vector_grid_why(window, cfg, &why, &ht)) {
+        if (height < window || width < window)
+            why = std::to_string(height) + " x " + std::to_string(width) + " is smaller than the window " +
+                  std::to_string(window);
+        else if (window_list_why(windows, window, height, width, &why) && windows && windows->N > 0 &&
+                 (!vectors || !fft_max))
+            why = "NULL vectors or fft_max";
+    }
+    if (!why.empty()) {
+        set_error("phd_debug_window_vectors_host: " + why);
+        return -1;
+    }
+    if (!windows || windows->N == 0) return 0;
+    const int nbins = cfg->angle_partitions * cfg->radius_partitions;
+    std::vector<unsigned long long> sums(nbins);
+    for (int k = 0; k < windows->N; k++) {
+        window_bins_host(window, rgb + 3LL * ((long long)windows->top[k] * width + windows->left[k]), 3LL * width,
+                         ht->t.map.data(), nbins, sums.data(), &fft_max[k]);
+        window_finish_host(ht->t, sums.data(), fft_max[k], window, *cfg, nullptr, vectors + (size_t)k * 10);
+    }
+    return 0;
+}
+
+// The shared finish alone over caller-given bin sums of one window.
+extern "C" int phd_debug_window_finish_host(const unsigned long long* bin_sums, double fft_max, int window,
+                                            const phd_config* cfg, double* bins, Blur_Vector* vectors) {
+    clear_error();
+    std::string why;
+    const HostTable* ht = nullptr;
+    if (!bin_sums || !vectors) why = "NULL bin_sums or vectors";
+    else vector_grid_why(window, cfg, &why, &ht);
+    if (!why.empty()) {
+        set_error("phd_debug_window_finish_host: " + why);
+        return -1;
+    }
+    window_finish_host(ht->t, bin_sums, fft_max, window, *cfg, bins, vectors);
     return 0;
 }
 

@@ -315,6 +315,19 @@ struct WinRec {
 };
 hipError_t launch_window_blur(int T, const WinRec* d_recs, int n, const double2* d_tw, const uint16_t* d_binmap,
                               int nbins, unsigned long long* d_bins, double* d_fmax, hipStream_t st);
+// The same steps, then the finish in the block (k_window_vectors): per window its
+// ten Blur_Vectors to d_dst[w].vectors (4-byte aligned) and its spectrum maximum
+// to d_dst[w].fft_max (8-byte aligned, or NULL); the bins stay in LDS.
+// d_counts: the table's elements per bin as u16 (at most T (T/2+1) = 8320); na >= 2.
+constexpr int kProfWindowVectors = 15;
+struct WinVector;              // blur_window.h: Blur_Vector's layout
+struct WinDst {
+    WinVector* vectors;
+    double* fft_max;
+};
+hipError_t launch_window_vectors(int T, const WinRec* d_recs, const WinDst* d_dst, int n, const double2* d_tw,
+                                 const uint16_t* d_binmap, const uint16_t* d_counts, int na, int nr, int denom,
+                                 double streak, double mag, hipStream_t st);
 void window_twiddles(int T, double2* tw);   // tw[e] = exp(-2 pi i e / T), e < T
 // The kernel's steps on the host for one window (host memory; binmap: the
 // table's host map): the same plan, passes and index maps, the C library's log.
