@@ -221,6 +221,52 @@ def normalize_salient(salient_characters, n):
     return arr, keep
 
 
+def _packed_images(images, nonempty=True, cuda=False, batch_error=None):
+    """The packed uint8 [H, W, 3] tensors of a call as a list: a 4-D tensor is
+    taken as its images (batch_error: what any other single tensor raises).
+    nonempty / cuda: whether empty tensors and tensors off the GPU are refused."""
+    import torch
+    if isinstance(images, torch.Tensor):
+        if images.dim() == 4:
+            images = images.unbind(0)
+        elif batch_error:
+            raise ValueError(batch_error)
+    images = list(images)
+    for im in images:
+        if not isinstance(im, torch.Tensor) or im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 \
+                or not im.is_contiguous() or (nonempty and im.numel() == 0) or (cuda and not im.is_cuda):
+            raise ValueError(f"expected contiguous{', non-empty' if nonempty else ''} uint8 [H, W, 3] device tensors")
+    return images
+
+
+def _image_arrays(images, ptr=lambda im: im.data_ptr()):
+    """(pointers, heights, widths) of 2-D or [H, W, ...] images as C arrays."""
+    n = len(images)
+    return ((ctypes.c_void_p * n)(*[ptr(im) for im in images]),
+            (ctypes.c_int * n)(*[int(im.shape[0]) for im in images]),
+            (ctypes.c_int * n)(*[int(im.shape[1]) for im in images]))
+
+
+def _window_entries(windows, n):
+    """The per-image window lists of a call over n images (None: none for any)."""
+    entries = list(windows) if windows is not None else [None] * n
+    if len(entries) != n:
+        raise ValueError(f"windows has {len(entries)} entries for {n} images")
+    return entries
+
+
+def _window_array(entries):
+    """The window lists of a call as the C argument: (array of
+    POINTER(Crop_Boundaries), the Crop_Boundaries to keep alive, None entries
+    for images without windows)."""
+    keep = [None if e is None else window_boundaries(e) for e in entries]
+    arr = (POINTER(Crop_Boundaries) * len(keep))()
+    for i, cb in enumerate(keep):
+        if cb is not None:
+            arr[i] = ctypes.pointer(cb)
+    return arr, keep
+
+
 def get_reports(images, salient_characters=None, **kw):
     """Reports for a list of images (any sizes).  Failed images give None.
     salient_characters: per-image crop boxes (normalize_salient)."""
@@ -228,9 +274,7 @@ def get_reports(images, salient_characters=None, **kw):
     arrs = [to_rgb8(im) for im in images]
     n = len(arrs)
     crops = normalize_salient(salient_characters, n)
-    ptrs = (ctypes.c_void_p * n)(*[a.ctypes.data for a in arrs])
-    hs = (ctypes.c_int * n)(*[a.shape[0] for a in arrs])
-    ws = (ctypes.c_int * n)(*[a.shape[1] for a in arrs])
+    ptrs, hs, ws = _image_arrays(arrs, lambda a: a.ctypes.data)
     outs = (POINTER(Full_Report_Data) * n)()
     st = (ctypes.c_int * n)()
     if crops is None:
@@ -307,9 +351,7 @@ def reports_device_mixed(images, stream=None, salient_characters=None, **kw):
     n = len(images)
     cfg = make_config(**kw)
     crops = normalize_salient(salient_characters, n)
-    ptrs = (ctypes.c_void_p * n)(*[im.data_ptr() for im in images])
-    hs = (ctypes.c_int * n)(*[int(im.shape[0]) for im in images])
-    ws = (ctypes.c_int * n)(*[int(im.shape[1]) for im in images])
+    ptrs, hs, ws = _image_arrays(images)
     s = _stream_handle(stream)
 
     def call(outs, st):
@@ -337,53 +379,11 @@ def reports_device_labels(images, stream=None, salient_characters=None, box_pale
     [n_boxes, 7] array (Br Bg Bb Cr Cg Cb and the average saturation of each
     salient_characters box at full resolution) as box_stats_device returns it
     (phd_report_batch_device_mixed_box_stats)."""
-    import torch
-    if isinstance(images, torch.Tensor):
-        if images.dim() != 4:
-            raise ValueError("expected a uint8 [N, H, W, 3] device tensor or a list of [H, W, 3] tensors")
-        images = list(images.unbind(0))
-    images = list(images)
-    for im in images:
-        if not isinstance(im, torch.Tensor) or im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 \
-                or not im.is_contiguous():
-            raise ValueError("expected contiguous uint8 [H, W, 3] device tensors")
-    n = len(images)
-    cfg = make_config(**kw)
-    crops = normalize_salient(salient_characters, n)
-    if n == 0:
-        return ([],) * (2 + bool(box_palettes) + bool(box_stats))
-    r = max(1, int(cfg.downsample_rate))
-    sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
-    labels = [torch.empty((h // r, w // r) if r > 1 else (h, w), dtype=torch.int16, device=im.device)
-              for im, (h, w) in zip(images, sizes)]
-    ptrs = (ctypes.c_void_p * n)(*[im.data_ptr() for im in images])
-    hs = (ctypes.c_int * n)(*[h for h, _ in sizes])
-    ws = (ctypes.c_int * n)(*[w for _, w in sizes])
-    maps = (ctypes.c_void_p * n)(*[m.data_ptr() for m in labels])
-    s = _stream_handle(stream)
-
-    def call(outs, st):
-        lib.phd_report_batch_device_mixed_labels(ptrs, hs, ws, n, ctypes.byref(cfg), crops[0] if crops else None,
-                                                 maps, outs, st, s)
-
-    if not box_palettes and not box_stats:
-        return _run_reports(call, "reports_device_labels", n, sizes, kw), labels
-    bp = (PhdBoxPalette * n)() if box_palettes else None
-    bs = (PhdBoxStats * n)() if box_stats else None
-    try:
-        if box_stats:
-            reps = _run_reports(lambda outs, st: lib.phd_report_batch_device_mixed_box_stats(
-                ptrs, hs, ws, n, ctypes.byref(cfg), crops[0] if crops else None, maps, bp, bs, outs, st, s),
-                "reports_device_labels", n, sizes, kw)
-        else:
-            reps = _run_reports(lambda outs, st: lib.phd_report_batch_device_mixed_box_palettes(
-                ptrs, hs, ws, n, ctypes.byref(cfg), crops[0] if crops else None, maps, bp, outs, st, s),
-                "reports_device_labels", n, sizes, kw)
-    except RuntimeError:
-        _free_boxes(bp, bs, n)
-        raise
-    return (reps, labels) + ((_take_box_palettes(bp, n),) if box_palettes else ()) + \
-        ((_take_box_stats(bs, n),) if box_stats else ())
+    images = _packed_images(images, nonempty=False,
+                            batch_error="expected a uint8 [N, H, W, 3] device tensor or a list of [H, W, 3] tensors")
+    ptrs, hs, ws = _image_arrays(images)
+    return _report_views("mixed", "reports_device_labels", (ptrs, hs, ws, len(images)), list(zip(hs, ws)), stream,
+                         salient_characters, kw, [im.device for im in images], box_palettes, box_stats)
 
 
 def quantize_device(labels, reports, none_rgb=(0, 0, 0), stream=None):
@@ -410,9 +410,7 @@ def quantize_device(labels, reports, none_rgb=(0, 0, 0), stream=None):
     luts = [np.array([[int(c) for c in col] for col in rep.color_palette.colors], dtype=np.uint8).reshape(-1, 3)
             for rep in reports]
     out = [torch.empty((m.shape[0], m.shape[1], 3), dtype=torch.uint8, device=m.device) for m in labels]
-    maps = (ctypes.c_void_p * n)(*[m.data_ptr() for m in labels])
-    hs = (ctypes.c_int * n)(*[int(m.shape[0]) for m in labels])
-    ws = (ctypes.c_int * n)(*[int(m.shape[1]) for m in labels])
+    maps, hs, ws = _image_arrays(labels)
     lut_ptrs = (ctypes.c_void_p * n)(*[(a.ctypes.data if a.size else None) for a in luts])
     ns = (ctypes.c_int * n)(*[a.shape[0] for a in luts])
     dst = (ctypes.c_void_p * n)(*[o.data_ptr() for o in out])
@@ -472,21 +470,12 @@ def box_stats_device(images, boxes, stream=None):
     accepts, in image coordinates (rows top <= y < bottom, columns left <= x <
     right; None or an empty list: no boxes, an array of shape (0, 7)).  One
     launch sums every box of every image."""
-    import torch
-    if isinstance(images, torch.Tensor) and images.dim() == 4:
-        images = list(images.unbind(0))
-    images = list(images)
-    for im in images:
-        if not isinstance(im, torch.Tensor) or im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 \
-                or not im.is_contiguous() or im.numel() == 0:
-            raise ValueError("expected contiguous, non-empty uint8 [H, W, 3] device tensors")
+    images = _packed_images(images)
     n = len(images)
     crops = normalize_salient(boxes if boxes is not None else [None] * n, n)
     if n == 0:
         return []
-    ptrs = (ctypes.c_void_p * n)(*[im.data_ptr() for im in images])
-    hs = (ctypes.c_int * n)(*[int(im.shape[0]) for im in images])
-    ws = (ctypes.c_int * n)(*[int(im.shape[1]) for im in images])
+    ptrs, hs, ws = _image_arrays(images)
     bs = (PhdBoxStats * n)()
     if lib.phd_box_stats_device(ptrs, hs, ws, n, crops[0], bs, _stream_handle(stream)) != 0:
         raise RuntimeError(f"box_stats_device failed: {last_error()}")
@@ -516,57 +505,52 @@ def box_palettes_device(labels, reports_or_n_slots, boxes, stream=None):
         return []
     ns = (ctypes.c_int * n)(*[(int(s) if isinstance(s, (int, np.integer)) else len(s.color_palette.colors))
                               for s in slots])
-    maps = (ctypes.c_void_p * n)(*[m.data_ptr() for m in labels])
-    hs = (ctypes.c_int * n)(*[int(m.shape[0]) for m in labels])
-    ws = (ctypes.c_int * n)(*[int(m.shape[1]) for m in labels])
+    maps, hs, ws = _image_arrays(labels)
     bp = (PhdBoxPalette * n)()
     if lib.phd_box_palettes_device(maps, hs, ws, n, ns, crops[0], bp, _stream_handle(stream)) != 0:
         raise RuntimeError(f"box_palettes_device failed: {last_error()}")
     return _take_box_palettes(bp, n)
 
 
-def _report_views(entry, name, views, n, stream, salient_characters, kw, label_entry=None, devices=None,
-                  box_entry=None, stats_entry=None):
-    """reports_device_views, _typed and _yuv after their descriptors are made.
-    devices (labels=True): the maps are allocated here as reports_device_labels
-    allocates its own, image i's on devices[i], and filled by label_entry, the
-    entry's _labels form.  box_entry (box_palettes=True): its _box_palettes
-    form; the box palettes are appended to the result.  Returns the reports,
-    (reports, maps), (reports, palettes) or (reports, maps, palettes).
-    stats_entry (box_stats=True): the entry's _box_stats form, which takes the
-    box palettes too (or none); the box statistics are appended last."""
+def _report_views(family, name, head, sizes, stream, salient_characters, kw, devices=None, box_palettes=False,
+                  box_stats=False):
+    """The four reports_device_* wrappers after their inputs are made: the C
+    call of `family` ("mixed", "views", "typed_views", "yuv") whose leading
+    arguments are `head` -- (pointers, heights, widths, n) or (descriptors, n)
+    -- over images of sizes[i] = (height, width).  devices (labels=True): image
+    i's label map is allocated here on devices[i].  The entry called is the
+    least that takes what was asked for: the plain one, _labels, _box_palettes
+    (with or without maps) or _box_stats (with or without either).  Returns
+    the reports, or a tuple of them and, in this order, the maps, the box
+    palettes and the box statistics that were asked for."""
+    n = len(sizes)
     cfg = make_config(**kw)
     crops = normalize_salient(salient_characters, n)
     want_maps = devices is not None
-    if n == 0 and (want_maps or box_entry is not None or stats_entry is not None):
-        return ([],) * (1 + want_maps + (box_entry is not None) + (stats_entry is not None))
+    extras = want_maps + bool(box_palettes) + bool(box_stats)
+    if n == 0 and extras:
+        return ([],) * (1 + extras)
     s = _stream_handle(stream)
-    if not want_maps and box_entry is None and stats_entry is None:
-        return _run_reports(lambda outs, st: entry(views, n, ctypes.byref(cfg), crops[0] if crops else None, outs, st,
-                                                   s), name, n, _view_sizes(views, n), kw)
-    sizes = _view_sizes(views, n)
-    labels, maps = None, None
+    labels = maps = None
     if want_maps:
         import torch
         r = max(1, int(cfg.downsample_rate))
         labels = [torch.empty((h // r, w // r) if r > 1 else (h, w), dtype=torch.int16, device=dev)
                   for (h, w), dev in zip(sizes, devices)]
         maps = (ctypes.c_void_p * n)(*[m.data_ptr() for m in labels])
-    if box_entry is None and stats_entry is None:
-        return _run_reports(lambda outs, st: label_entry(views, n, ctypes.byref(cfg), crops[0] if crops else None,
-                                                         maps, outs, st, s), name, n, sizes, kw), labels
-    bp = (PhdBoxPalette * n)() if box_entry is not None else None
-    bs = (PhdBoxStats * n)() if stats_entry is not None else None
+    bp = (PhdBoxPalette * n)() if box_palettes else None
+    bs = (PhdBoxStats * n)() if box_stats else None
+    suffix, tail = ("_box_stats", (maps, bp, bs)) if box_stats else ("_box_palettes", (maps, bp)) if box_palettes \
+        else ("_labels", (maps,)) if want_maps else ("", ())
+    entry = getattr(lib, f"phd_report_batch_device_{family}{suffix}")
     try:
-        if stats_entry is not None:
-            reps = _run_reports(lambda outs, st: stats_entry(views, n, ctypes.byref(cfg), crops[0] if crops else None,
-                                                             maps, bp, bs, outs, st, s), name, n, sizes, kw)
-        else:
-            reps = _run_reports(lambda outs, st: box_entry(views, n, ctypes.byref(cfg), crops[0] if crops else None,
-                                                           maps, bp, outs, st, s), name, n, sizes, kw)
+        reps = _run_reports(lambda outs, st: entry(*head, ctypes.byref(cfg), crops[0] if crops else None, *tail, outs,
+                                                   st, s), name, n, sizes, kw)
     except RuntimeError:
         _free_boxes(bp, bs, n)
         raise
+    if not extras:
+        return reps
     return (reps,) + ((labels,) if want_maps else ()) + ((_take_box_palettes(bp, n),) if bp is not None else ()) + \
         ((_take_box_stats(bs, n),) if bs is not None else ())
 
@@ -663,14 +647,9 @@ def reports_device_views(images, layout="HWC", bgr=False, stream=None, salient_c
     and the average saturation of each box at full resolution) as
     box_stats_device returns it (phd_report_batch_device_views_box_stats)."""
     views, keep = make_views(images, layout, bgr)
-    if not labels and not box_palettes and not box_stats:
-        return _report_views(lib.phd_report_batch_device_views, "reports_device_views", views, len(keep), stream,
-                             salient_characters, kw)
-    return _report_views(None, "reports_device_views", views, len(keep), stream, salient_characters, kw,
-                         lib.phd_report_batch_device_views_labels,
-                         _label_devices(keep, lambda t: t) if labels else None,
-                         lib.phd_report_batch_device_views_box_palettes if box_palettes else None,
-                         lib.phd_report_batch_device_views_box_stats if box_stats else None)
+    n = len(keep)
+    return _report_views("views", "reports_device_views", (views, n), _view_sizes(views, n), stream, salient_characters,
+                         kw, _label_devices(keep, lambda t: t) if labels else None, box_palettes, box_stats)
 
 
 def pack_views_device(images, layout="HWC", bgr=False, stream=None):
@@ -750,14 +729,10 @@ def reports_device_typed(images, layout="HWC", bgr=False, max_value=None, snap_u
     reports_device_views appends them; an fp64-route image's are the fp64
     functions on its doubles (phd_report_batch_device_typed_views_box_stats)."""
     views, keep = make_typed_views(images, layout, bgr, max_value, snap_u8)
-    if not labels and not box_palettes and not box_stats:
-        return _report_views(lib.phd_report_batch_device_typed_views, "reports_device_typed", views, len(keep),
-                             stream, salient_characters, kw)
-    return _report_views(None, "reports_device_typed", views, len(keep), stream, salient_characters, kw,
-                         lib.phd_report_batch_device_typed_views_labels,
-                         _label_devices(keep, lambda t: t) if labels else None,
-                         lib.phd_report_batch_device_typed_views_box_palettes if box_palettes else None,
-                         lib.phd_report_batch_device_typed_views_box_stats if box_stats else None)
+    n = len(keep)
+    return _report_views("typed_views", "reports_device_typed", (views, n), _view_sizes(views, n), stream,
+                         salient_characters, kw, _label_devices(keep, lambda t: t) if labels else None, box_palettes,
+                         box_stats)
 
 
 def decode_views_device(images, layout="HWC", bgr=False, max_value=None, stream=None):
@@ -870,14 +845,10 @@ def reports_device_yuv(frames, matrix="bt601", full_range=True, chroma="replicat
     statistics of the RGB8 conversion are appended last as reports_device_views
     appends them (phd_report_batch_device_yuv_box_stats)."""
     views, keep = make_yuv_views(frames, matrix, full_range, chroma, swap_uv)
-    if not labels and not box_palettes and not box_stats:
-        return _report_views(lib.phd_report_batch_device_yuv, "reports_device_yuv", views, len(keep), stream,
-                             salient_characters, kw)
-    return _report_views(None, "reports_device_yuv", views, len(keep), stream, salient_characters, kw,
-                         lib.phd_report_batch_device_yuv_labels,
+    n = len(keep)
+    return _report_views("yuv", "reports_device_yuv", (views, n), _view_sizes(views, n), stream, salient_characters, kw,
                          _label_devices(keep, lambda f: f[0] if isinstance(f, (tuple, list)) else f) if labels
-                         else None, lib.phd_report_batch_device_yuv_box_palettes if box_palettes else None,
-                         lib.phd_report_batch_device_yuv_box_stats if box_stats else None)
+                         else None, box_palettes, box_stats)
 
 
 def convert_yuv_device(frames, matrix="bt601", full_range=True, chroma="replicate", swap_uv=False, stream=None):
@@ -989,29 +960,14 @@ def blur_windows_device(images, windows, window=128, stream=None, **kw):
     parameters; radius_partitions and angle_partitions default to 16 and 36 here
     (the report's 40 x 72 leaves most bins of a small spectrum empty and has no
     table at 64).  One launch takes every window of every image."""
-    import torch
-    if isinstance(images, torch.Tensor) and images.dim() == 4:
-        images = list(images.unbind(0))
-    images = list(images)
-    for im in images:
-        if not isinstance(im, torch.Tensor) or im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 \
-                or not im.is_contiguous() or im.numel() == 0:
-            raise ValueError("expected contiguous, non-empty uint8 [H, W, 3] device tensors")
+    images = _packed_images(images)
     n = len(images)
-    entries = list(windows) if windows is not None else [None] * n
-    if len(entries) != n:
-        raise ValueError(f"windows has {len(entries)} entries for {n} images")
+    entries = _window_entries(windows, n)
     cfg = make_config(**{**WINDOW_DEFAULTS, **kw})
     if n == 0:
         return []
-    keep = [None if e is None else window_boundaries(e) for e in entries]
-    arr = (POINTER(Crop_Boundaries) * n)()
-    for i, cb in enumerate(keep):
-        if cb is not None:
-            arr[i] = ctypes.pointer(cb)
-    ptrs = (ctypes.c_void_p * n)(*[im.data_ptr() for im in images])
-    hs = (ctypes.c_int * n)(*[int(im.shape[0]) for im in images])
-    ws = (ctypes.c_int * n)(*[int(im.shape[1]) for im in images])
+    arr, keep = _window_array(entries)
+    ptrs, hs, ws = _image_arrays(images)
     wb = (PhdWindowBlur * n)()
     if lib.phd_blur_windows_device(ptrs, hs, ws, n, arr, int(window), ctypes.byref(cfg), wb,
                                    _stream_handle(stream)) != 0:
@@ -1056,18 +1012,6 @@ def blur_map_device(images, window=128, stride=None, stream=None, **kw):
     return [tuple(a.reshape(g[1] + a.shape[1:]) for a in r) for r, g in zip(res, grids)]
 
 
-def _window_images(images):
-    import torch
-    if isinstance(images, torch.Tensor) and images.dim() == 4:
-        images = list(images.unbind(0))
-    images = list(images)
-    for im in images:
-        if not isinstance(im, torch.Tensor) or im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 \
-                or not im.is_contiguous() or im.numel() == 0 or not im.is_cuda:
-            raise ValueError("expected contiguous, non-empty uint8 [H, W, 3] device tensors")
-    return images
-
-
 def _blur_vectors_call(images, counts, shapes, stream, call):
     """The device tensors of a blur vectors call and the call itself: per image
     (angles, magnitudes, fft_max) shaped shapes[i] + (10,), (10,), ()."""
@@ -1078,9 +1022,7 @@ def _blur_vectors_call(images, counts, shapes, stream, call):
     if stream is not None:
         for t in vec + fmax:
             t.record_stream(stream)
-    ptrs = (ctypes.c_void_p * n)(*[im.data_ptr() for im in images])
-    hs = (ctypes.c_int * n)(*[int(im.shape[0]) for im in images])
-    ws = (ctypes.c_int * n)(*[int(im.shape[1]) for im in images])
+    ptrs, hs, ws = _image_arrays(images)
     pv = (ctypes.c_void_p * n)(*[v.data_ptr() if c else None for v, c in zip(vec, counts)])
     pf = (ctypes.c_void_p * n)(*[f.data_ptr() if c else None for f, c in zip(fmax, counts)])
     call(ptrs, hs, ws, n, pv, pf, _stream_handle(stream))
@@ -1099,19 +1041,13 @@ def blur_vectors_device(images, windows, window=128, stream=None, **kw):
     Inputs and kw as blur_windows_device; angle_partitions must be at least 2.
     Nothing is copied to the host; with stream= the call is enqueued on that
     stream and the tensors are valid in its order."""
-    images = _window_images(images)
+    images = _packed_images(images, cuda=True)
     n = len(images)
-    entries = list(windows) if windows is not None else [None] * n
-    if len(entries) != n:
-        raise ValueError(f"windows has {len(entries)} entries for {n} images")
+    entries = _window_entries(windows, n)
     cfg = make_config(**{**WINDOW_DEFAULTS, **kw})
     if n == 0:
         return []
-    keep = [None if e is None else window_boundaries(e) for e in entries]
-    arr = (POINTER(Crop_Boundaries) * n)()
-    for i, cb in enumerate(keep):
-        if cb is not None:
-            arr[i] = ctypes.pointer(cb)
+    arr, keep = _window_array(entries)
     counts = [0 if cb is None else int(cb.N) for cb in keep]
 
     def call(ptrs, hs, ws, n, pv, pf, s):
@@ -1127,7 +1063,7 @@ def blur_vector_maps_device(images, window=128, stride=None, stream=None, **kw):
     [gh, gw, 10] int32, magnitudes [gh, gw, 10] float32, fft_max [gh, gw]
     float64) -- blur_map_device's vectors and maxima without its bins, and
     without a copy to the host."""
-    images = _window_images(images)
+    images = _packed_images(images, cuda=True)
     n = len(images)
     stride = window if stride is None else int(stride)
     cfg = make_config(**{**WINDOW_DEFAULTS, **kw})

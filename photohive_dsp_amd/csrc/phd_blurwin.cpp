@@ -312,13 +312,9 @@ int blur_vectors_call(const char* entry, const uint8_t* const* d_images, const i
     auto run = [&]() {
         const BlurTable* tbl = get_table(c, T, T, nr, na);
         if (!tbl) return false;
-        // upload_table's rule (phd_inputs.cpp), filled in place: the last launch that read the context's
-        // table may still run on a caller's stream that nobody has drained
-        if (!c->ev_views) PHD_HIP(hipEventCreateWithFlags(&c->ev_views, hipEventDisableTiming));
-        else PHD_HIP(hipEventSynchronize(c->ev_views));
-        if (!ensure_device(&c->d_views, &c->views_bytes, bytes)) return false;
-        if (!grow_pinned(&c->h_views, &c->h_views_bytes, bytes)) return false;
-        uint8_t* h = (uint8_t*)c->h_views;
+        // the context's launch table, filled in place
+        uint8_t* h = (uint8_t*)table_begin(c, bytes);
+        if (!h) return false;
         uint8_t* d = (uint8_t*)c->d_views;
         memset(h, 0, o_recs);
         window_twiddles(T, (double2*)h);
@@ -338,7 +334,7 @@ int blur_vectors_call(const char* entry, const uint8_t* const* d_images, const i
                                 d_fft_max && d_fft_max[i] ? d_fft_max[i] + k : nullptr};
             }
         }
-        PHD_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st));
+        if (!table_upload(c, bytes, st)) return false;
         const int ps = c->prof.begin(kWindowVectors, st);
         const hipError_t e = launch_window_vectors(T, (const WinRec*)(d + o_recs), (const WinDst*)(d + o_dst), (int)nw,
                                                    (const double2*)d, tbl->d_map, (const uint16_t*)(d + o_counts), na,

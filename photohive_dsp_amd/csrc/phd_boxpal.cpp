@@ -96,10 +96,13 @@ bool enqueue_box_job(Context* c, const BoxJob& job, hipStream_t st) {
         }
         const size_t o_items = al(sizeof(BoxRec) * job.recs.size());
         const size_t bytes = o_items + sizeof(BoxItem) * job.items.size();
-        std::vector<uint8_t> tab(bytes);
-        memcpy(tab.data(), job.recs.data(), sizeof(BoxRec) * job.recs.size());
-        memcpy(tab.data() + o_items, job.items.data(), sizeof(BoxItem) * job.items.size());
-        if (!upload_table(c, tab.data(), bytes, bytes, st)) return false;
+        uint8_t* tab = (uint8_t*)table_begin(c, bytes);
+        if (!tab) return false;
+        const size_t rbytes = sizeof(BoxRec) * job.recs.size();
+        memcpy(tab, job.recs.data(), rbytes);
+        memset(tab + rbytes, 0, o_items - rbytes);
+        memcpy(tab + o_items, job.items.data(), sizeof(BoxItem) * job.items.size());
+        if (!table_upload(c, bytes, st)) return false;
         const int ps = c->prof.begin(kBoxPalettes, st);
         PHD_HIP(launch_box_counts((const BoxRec*)c->d_views, (const BoxItem*)((const uint8_t*)c->d_views + o_items),
                                   (int)job.items.size(), (unsigned*)c->d_boxpal, st));

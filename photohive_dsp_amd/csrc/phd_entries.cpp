@@ -474,6 +474,31 @@ static std::vector<int> valid_box_images(const Crop_Boundaries* const* crops, co
 
 namespace phd {
 
+// The entry a report call's messages name: the most derived output present
+// picks it (a NULL output is one the entry does not take); with none, `plain`
+// -- "" for the family's plain entry, what the mixed entries pass otherwise.
+std::string entry_name(const char* family, const char* plain, const CallOutputs& outs) {
+    return std::string("phd_report_batch_device_") + family +
+           (outs.box_stats ? "_box_stats" : outs.box_palettes ? "_box_palettes" : outs.d_labels ? "_labels" : plain);
+}
+
+// What every entry that can take outputs does first: the caller's structs zeroed,
+// then the argument check (args_ok) and the label slots' rule, no HIP call yet.
+bool report_prologue(const std::string& entry, bool args_ok, int n_images, const phd_config* cfg,
+                     const CallOutputs& outs) {
+    clear_error();
+    outs.reset(n_images);
+    if (!args_ok) {
+        set_error(entry + ": bad arguments");
+        return false;
+    }
+    if (outs.needs_label_slots() && make_grid(*cfg).tl >= 32768) {
+        set_error(entry + ": label maps need fewer than 32768 octree groups (palette slots)");
+        return false;
+    }
+    return true;
+}
+
 // One group of a batch large enough for two lanes (two-lane calls on the
 // library's streams only): two groups in lane_split's proportion, one per lane.
 void split_for_lanes(std::vector<std::vector<int>>* groups, void* stream) {
@@ -505,24 +530,15 @@ void report_group(Context* cl, const std::vector<BatchImage>& imgs, const std::v
     if (m == 0) return;
     std::vector<const uint8_t*> rp(m);
     std::vector<const Crop_Boundaries*> cr(m);
-    std::vector<uint16_t*> lab(m);
-    std::vector<phd_box_palette*> bp(m);
-    std::vector<phd_box_stats*> bs(m);
-    bool maps = false, pals = false, stats = false;
+    std::vector<ImageOutputs> outs(m);
     for (int q = 0; q < m; q++) {
         rp[q] = ptrs[ks[q]];
         cr[q] = imgs[grp[ks[q]]].boxes;
-        lab[q] = imgs[grp[ks[q]]].labels;
-        bp[q] = imgs[grp[ks[q]]].box_pal;
-        maps = maps || lab[q];
-        pals = pals || bp[q];
-        bs[q] = imgs[grp[ks[q]]].box_stats;
-        stats = stats || bs[q];
+        outs[q] = imgs[grp[ks[q]]].outs;
     }
     RunResults rr(m);
     run_reports(cl, rp.data(), m, imgs[grp[0]].height, imgs[grp[0]].width, cfg, nullptr, rr.o.data(), rr.st.data(),
-                (hipStream_t)stream, boxes ? cr.data() : nullptr, maps ? lab.data() : nullptr,
-                pals ? bp.data() : nullptr, stats ? bs.data() : nullptr);
+                (hipStream_t)stream, boxes ? cr.data() : nullptr, outs.data());
     for (int q = 0; q < m; q++) {
         r->o[ks[q]] = rr.o[q];
         r->st[ks[q]] = rr.st[q];
@@ -607,31 +623,19 @@ extern "C" int phd_report_batch_device_crops(const uint8_t* d_rgb, int n_images,
 // Device-resident images of any sizes (BASELINE config 5): one batched run
 // (K1, FFTs, palette tail, per-image read-back) per group of same-size images.
 // A single size group is not split across lanes.
-static int report_mixed(const char* entry, const uint8_t* const* d_images, const int* heights, const int* widths,
+// plain: what the entry's name ends in when the call has no outputs (entry_name).
+static int report_mixed(const char* plain, const uint8_t* const* d_images, const int* heights, const int* widths,
                         int n_images, const phd_config* cfg, const Crop_Boundaries* const* crops,
-                        Full_Report_Data** out, int* status, void* stream, uint16_t* const* d_labels = nullptr,
-                        phd_box_palette* box_palettes = nullptr, phd_box_stats* box_stats = nullptr) {
-    clear_error();
-    if (box_palettes && n_images > 0)
-        for (int i = 0; i < n_images; i++) box_palettes[i] = phd_box_palette{0, 0, nullptr};
-    if (box_stats && n_images > 0)
-        for (int i = 0; i < n_images; i++) box_stats[i] = phd_box_stats{0, nullptr, nullptr};
-    if (!d_images || !heights || !widths || !cfg || !out || !status || n_images <= 0) {
-        set_error(std::string(entry) + ": bad arguments");
+                        const CallOutputs& outs, Full_Report_Data** out, int* status, void* stream) {
+    if (!report_prologue(entry_name("mixed", plain, outs),
+                         d_images && heights && widths && cfg && out && status && n_images > 0, n_images, cfg, outs))
         return -1;
-    }
-    // a label is a palette slot below PHD_LABEL_NONE's sign bit (int16 readers)
-    if ((d_labels || box_palettes) && make_grid(*cfg).tl >= 32768) {
-        set_error(std::string(entry) + ": label maps need fewer than 32768 octree groups (palette slots)");
-        return -1;
-    }
     Context* c = get_context();
     if (!c) return -1;
     std::vector<BatchImage> imgs;
     for (int i : valid_box_images(crops, heights, widths, 0, 0, n_images, out, status))
         imgs.push_back({i, BatchImage::kPacked, d_images[i], heights[i], widths[i], crops ? crops[i] : nullptr,
-                        d_labels ? d_labels[i] : nullptr, box_palettes ? box_palettes + i : nullptr,
-                        box_stats ? box_stats + i : nullptr});
+                        outs.of(i)});
     return run_device_batch(c, imgs, mixed_groups(imgs), run_packed_group, crops != nullptr, *cfg, out, status,
                             n_images, stream);
 }
@@ -639,56 +643,48 @@ static int report_mixed(const char* entry, const uint8_t* const* d_images, const
 extern "C" int phd_report_batch_device_mixed(const uint8_t* const* d_images, const int* heights, const int* widths,
                                              int n_images, const phd_config* cfg, Full_Report_Data** out,
                                              int* status, void* stream) {
-    return report_mixed("phd_report_batch_device_mixed", d_images, heights, widths, n_images, cfg, nullptr, out,
-                        status, stream);
+    return report_mixed("", d_images, heights, widths, n_images, cfg, nullptr, {}, out, status, stream);
 }
 
 extern "C" int phd_report_batch_device_mixed_crops(const uint8_t* const* d_images, const int* heights,
                                                    const int* widths, int n_images, const phd_config* cfg,
                                                    const Crop_Boundaries* const* crops, Full_Report_Data** out,
                                                    int* status, void* stream) {
-    return report_mixed(crops ? "phd_report_batch_device_mixed_crops" : "phd_report_batch_device_mixed", d_images,
-                        heights, widths, n_images, cfg, crops, out, status, stream);
+    return report_mixed(crops ? "_crops" : "", d_images, heights, widths, n_images, cfg, crops, {}, out, status,
+                        stream);
 }
 
 // phd_report_batch_device_mixed_crops plus each image's palette label map (the
 // parents' pixel lists after group_irregular_pixels,
-// src/color_quantization.c:342-479): the label launch follows the palette's
-// second pass of each run (ReportRun::label_maps).
+// src/color_quantization.c:342-479: ReportRun::label_maps), its box palette too
+// (_box_palettes: per crop box, the elements of every palette slot, counted
+// behind the label launch) and its box statistics too (_box_stats:
+// ReportRun::box_stat_job, beside the sharpness launch).  An output passed as
+// NULL is one the entry does not take.
 extern "C" int phd_report_batch_device_mixed_labels(const uint8_t* const* d_images, const int* heights,
                                                     const int* widths, int n_images, const phd_config* cfg,
                                                     const Crop_Boundaries* const* crops,
                                                     uint16_t* const* d_labels, Full_Report_Data** out, int* status,
                                                     void* stream) {
-    return report_mixed("phd_report_batch_device_mixed_labels", d_images, heights, widths, n_images, cfg, crops,
-                        out, status, stream, d_labels);
+    return report_mixed("_labels", d_images, heights, widths, n_images, cfg, crops, {d_labels}, out, status, stream);
 }
 
-// ... plus each image's box palette: per crop box, the elements of every
-// palette slot (ReportRun::label_maps counts behind the label launch).
-// box_palettes == NULL: exactly the call above.
 extern "C" int phd_report_batch_device_mixed_box_palettes(const uint8_t* const* d_images, const int* heights,
                                                           const int* widths, int n_images, const phd_config* cfg,
                                                           const Crop_Boundaries* const* crops,
                                                           uint16_t* const* d_labels, phd_box_palette* box_palettes,
                                                           Full_Report_Data** out, int* status, void* stream) {
-    return report_mixed(box_palettes ? "phd_report_batch_device_mixed_box_palettes"
-                                     : "phd_report_batch_device_mixed_labels",
-                        d_images, heights, widths, n_images, cfg, crops, out, status, stream, d_labels, box_palettes);
+    return report_mixed("_labels", d_images, heights, widths, n_images, cfg, crops, {d_labels, box_palettes}, out,
+                        status, stream);
 }
 
-// ... plus each image's box statistics (ReportRun::box_stat_job, beside the
-// sharpness launch).  box_stats == NULL: exactly the call above.
 extern "C" int phd_report_batch_device_mixed_box_stats(const uint8_t* const* d_images, const int* heights,
                                                        const int* widths, int n_images, const phd_config* cfg,
                                                        const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
                                                        phd_box_palette* box_palettes, phd_box_stats* box_stats,
                                                        Full_Report_Data** out, int* status, void* stream) {
-    if (!box_stats)
-        return phd_report_batch_device_mixed_box_palettes(d_images, heights, widths, n_images, cfg, crops, d_labels,
-                                                          box_palettes, out, status, stream);
-    return report_mixed("phd_report_batch_device_mixed_box_stats", d_images, heights, widths, n_images, cfg, crops,
-                        out, status, stream, d_labels, box_palettes, box_stats);
+    return report_mixed("_labels", d_images, heights, widths, n_images, cfg, crops,
+                        {d_labels, box_palettes, box_stats}, out, status, stream);
 }
 
 extern "C" int phd_report_batch_u8_crops(const uint8_t* const* images, const int* heights, const int* widths,

@@ -441,42 +441,67 @@ bool legacy_release(Full_Report_Data* r);
 // RGB8 pipeline when every value is k/255.0, else the fp64 planar kernels.
 Full_Report_Data* report_planar(Context* c, const double* r, const double* g, const double* b, int height,
                                 int width, const phd_config& cfg, const Crop_Boundaries* crops);
+// What a report call returns per image beside its report; every member optional
+// (NULL: not asked for).  One record from the entries to the stage that fills it.
+struct ImageOutputs {
+    // device: the palette label map, (height / ds) x (width / ds); complete when
+    // the run returns, untouched when the image fails before its palette decision
+    uint16_t* labels = nullptr;
+    // the caller's struct (zeroed by the entry): n_slots of a reported image and
+    // the counts of its boxes, from labels or from a scratch map of the context
+    // (Context::d_labscratch); a failed image keeps {0, 0, NULL}
+    phd_box_palette* box_pal = nullptr;
+    // the caller's struct (zeroed by the entry): the statistics of its boxes at
+    // full resolution; a failed image and one without boxes keep {0, NULL, NULL}
+    phd_box_stats* box_stats = nullptr;
+};
+// The same as the C ABI passes it for a whole call: arrays over the images, or NULL.
+struct CallOutputs {
+    uint16_t* const* d_labels = nullptr;
+    phd_box_palette* box_palettes = nullptr;
+    phd_box_stats* box_stats = nullptr;
+    ImageOutputs of(int i) const {
+        return {d_labels ? d_labels[i] : nullptr, box_palettes ? box_palettes + i : nullptr,
+                box_stats ? box_stats + i : nullptr};
+    }
+    // the caller's structs zeroed: before the argument check, so a failed call leaves nothing to free
+    void reset(int n) const {
+        for (int i = 0; i < n; i++) {
+            if (box_palettes) box_palettes[i] = phd_box_palette{0, 0, nullptr};
+            if (box_stats) box_stats[i] = phd_box_stats{0, nullptr, nullptr};
+        }
+    }
+    // a label is a palette slot below PHD_LABEL_NONE's sign bit (int16 readers):
+    // these outputs need fewer than 32768 octree groups
+    bool needs_label_slots() const { return d_labels || box_palettes; }
+};
 // report_planar after its upload: the fp64 planar pipeline on planes already
 // in c->d_planes (4 n doubles: P.r | P.g | P.b | luma) on the idle stream st;
 // cfg, the size and the boxes validated by the caller.  The typed entry runs
-// it on the planes k_decode_view filled.  labels (or NULL): the image's palette
-// label map (device), complete when the call returns.  box_pal (or NULL): the
-// image's box palette (zeroed by the caller), counted from labels or from a
-// map in Context::d_labscratch.  box_stats (or NULL): the image's box
-// statistics (zeroed by the caller) from the fp64 functions on the planes
-// (k_planar_box_stats, beside the sharpness crops); filled when the image reports.
+// it on the planes k_decode_view filled.  outs: ImageOutputs, the box
+// statistics from the fp64 functions on the planes (k_planar_box_stats).
 Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int height, int width, const phd_config& cfg,
-                                       const Crop_Boundaries* crops, hipStream_t st, uint16_t* labels,
-                                       phd_box_palette* box_pal = nullptr, phd_box_stats* box_stats = nullptr);
+                                       const Crop_Boundaries* crops, hipStream_t st, const ImageOutputs& outs);
 // Run the full report on n same-size device images.  out[i]/status[i] per image.
 // crops: one set of boxes for every image (the single-image entries; two
 // launches per box, sharpness.hip's k_sharp_pass).  img_crops (crops must be
 // NULL): image i's own boxes, NULL entries allowed, already validated
 // (crops_why); every box of the call goes through one batched launch.
-// labels (or NULL): image i's palette label map goes to labels[i] (device,
-// NULL entries allowed) on the tail stream after the palette's second pass;
-// complete when run_reports returns.
-// box_pal (or NULL): image i's box palette goes to *box_pal[i] (NULL entries
-// allowed; zeroed by the caller): n_slots for every reported image, the counts
-// of its img_crops boxes where it has any -- from labels[i], or from a scratch
-// map of the context (Context::d_labscratch) where the caller gave none.
-// box_stats (or NULL): image i's box statistics go to *box_stats[i] (NULL
-// entries allowed; zeroed by the caller) from its img_crops boxes, enqueued with
-// the sharpness launch; a failed image keeps {0, NULL, NULL}.
+// outs (or NULL: none): image i's ImageOutputs, n of them; the boxes of the box
+// palettes and statistics are the image's img_crops.
 bool run_reports(Context* c, const uint8_t* const* d_imgs, int n, int height, int width,
                  const phd_config& cfg, const Crop_Boundaries* crops, Full_Report_Data** out,
                  int* status, hipStream_t stream, const Crop_Boundaries* const* img_crops = nullptr,
-                 uint16_t* const* labels = nullptr, phd_box_palette* const* box_pal = nullptr,
-                 phd_box_stats* const* box_stats = nullptr);
+                 const ImageOutputs* outs = nullptr);
 // A launch table (phd_inputs.cpp): `bytes` go up on st into Context::d_views
-// through its pinned copy, the first `filled` from `host`, the rest zero, once
-// the last launch that read the table is done; table_launched: after the last
-// operation on st that reads it.
+// from its pinned copy Context::h_views.  table_begin returns that pinned block
+// (nullptr: error) once the last launch that read the table is done, to be
+// filled in place -- Context::d_views has its final address by then;
+// table_upload is the one copy; table_launched: after the last operation on st
+// that reads the table.  upload_table: the three steps with the first `filled`
+// bytes from `host`, the rest zero.
+void* table_begin(Context* c, size_t bytes);
+bool table_upload(Context* c, size_t bytes, hipStream_t st);
 bool upload_table(Context* c, const void* host, size_t filled, size_t bytes, hipStream_t st);
 bool table_launched(Context* c, hipStream_t st);
 // The batched sharpness stage of n same-size device images on st: uploads the
@@ -498,7 +523,7 @@ struct BoxJob {
     void add_image(const uint16_t* map, int mh, int mw, int ds, int n_slots, const Crop_Boundaries* b);
 };
 bool box_palette_fill(phd_box_palette* bp, int n_boxes, int n_slots, const uint32_t* h);
-// The job on st: its table goes up (upload_table), Context::d_boxpal is zeroed
+// The job on st: its table goes up (table_begin), Context::d_boxpal is zeroed
 // by one memset, one launch counts, one copy brings the counters to
 // Context::h_boxpal.  The caller waits for st before it reads them.
 bool enqueue_box_job(Context* c, const BoxJob& job, hipStream_t st);
@@ -535,9 +560,7 @@ struct BatchImage {
                                      // phd_typed_view or phd_yuv_view of it (staged on the lane)
     int height, width;
     const Crop_Boundaries* boxes;    // NULL: none
-    uint16_t* labels = nullptr;      // device: the image's label map, (height / ds) x (width / ds); NULL: none
-    phd_box_palette* box_pal = nullptr;   // the caller's struct for the image's box palette; NULL: none
-    phd_box_stats* box_stats = nullptr;   // the caller's struct for the image's box statistics; NULL: none
+    ImageOutputs outs{};             // what the call returns for it beside the report
 };
 // The reports and statuses of one run of m images, and their way back to the
 // caller's arrays: result k belongs to the caller's image idx[k].
@@ -567,6 +590,12 @@ void report_group(Context* cl, const std::vector<BatchImage>& imgs, const std::v
 int run_device_batch(Context* c, const std::vector<BatchImage>& imgs, const std::vector<std::vector<int>>& groups,
                      GroupFn run_group, bool boxes, const phd_config& cfg, Full_Report_Data** out, int* status,
                      int n_images, void* stream);
+// A report entry's name in its messages, from its family ("mixed", "views",
+// "typed_views", "yuv") and the outputs present, and the entries' shared first
+// steps: reset, argument check (args_ok), the label slots' rule (phd_entries.cpp)
+std::string entry_name(const char* family, const char* plain, const CallOutputs& outs);
+bool report_prologue(const std::string& entry, bool args_ok, int n_images, const phd_config* cfg,
+                     const CallOutputs& outs);
 // The same-size groups of the kept images of a mixed-size call, and one group
 // of a batch large enough for two lanes cut in two (views, typed and YUV calls)
 std::vector<std::vector<int>> mixed_groups(const std::vector<BatchImage>& imgs);

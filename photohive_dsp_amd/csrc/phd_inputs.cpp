@@ -15,20 +15,33 @@ using namespace phd;
 namespace phd {
 
 // ---- launch tables ------------------------------------------------------------
-// `bytes` of a launch table go up on st through the context's pinned copy
-// (d_views / h_views): the first `filled` bytes from `host`, the rest zero.
-// The table of the context's last launch is still read until that launch is
-// done (a caller's stream is not drained by the call that used it): ev_views,
-// recorded by table_launched, is waited for first.
-bool upload_table(Context* c, const void* host, size_t filled, size_t bytes, hipStream_t st) {
-    if (!c->ev_views) PHD_HIP(hipEventCreateWithFlags(&c->ev_views, hipEventDisableTiming));
-    else PHD_HIP(hipEventSynchronize(c->ev_views));
-    if (!ensure_device(&c->d_views, &c->views_bytes, bytes)) return false;
-    if (!grow_pinned(&c->h_views, &c->h_views_bytes, bytes)) return false;
-    memcpy(c->h_views, host, filled);
-    memset((uint8_t*)c->h_views + filled, 0, bytes - filled);
+// `bytes` of a launch table go up on st from the context's pinned copy
+// (d_views / h_views).  The table of the context's last launch is still read
+// until that launch is done (a caller's stream is not drained by the call
+// that used it): ev_views, recorded by table_launched, is waited for first --
+// here and nowhere else.  The pinned block to fill, or nullptr.
+void* table_begin(Context* c, size_t bytes) {
+    auto ready = [&]() {
+        if (!c->ev_views) PHD_HIP(hipEventCreateWithFlags(&c->ev_views, hipEventDisableTiming));
+        else PHD_HIP(hipEventSynchronize(c->ev_views));
+        return ensure_device(&c->d_views, &c->views_bytes, bytes) &&
+               grow_pinned(&c->h_views, &c->h_views_bytes, bytes);
+    };
+    return ready() ? c->h_views : nullptr;
+}
+
+bool table_upload(Context* c, size_t bytes, hipStream_t st) {
     PHD_HIP(hipMemcpyAsync(c->d_views, c->h_views, bytes, hipMemcpyHostToDevice, st));
     return true;
+}
+
+// The first `filled` bytes from `host`, the rest zero.
+bool upload_table(Context* c, const void* host, size_t filled, size_t bytes, hipStream_t st) {
+    uint8_t* h = (uint8_t*)table_begin(c, bytes);
+    if (!h) return false;
+    memcpy(h, host, filled);
+    memset(h + filled, 0, bytes - filled);
+    return table_upload(c, bytes, st);
 }
 
 // After the last operation on st that uses the table.
@@ -266,8 +279,7 @@ void run_typed_group(Context* cl, const std::vector<BatchImage>& imgs, const std
         Full_Report_Data* o = nullptr;
         if (enqueue_decode_view(cl, tv(k), dp, st))
             o = report_planes_device(cl, PlanarSrc{dp, dp + n, dp + 2 * n}, height, width, cfg,
-                                     boxes ? imgs[grp[k]].boxes : nullptr, st, imgs[grp[k]].labels,
-                                     imgs[grp[k]].box_pal, imgs[grp[k]].box_stats);
+                                     boxes ? imgs[grp[k]].boxes : nullptr, st, imgs[grp[k]].outs);
         (void)hipStreamSynchronize(st);
         cl->prof.collect();
         if (o) {
@@ -283,29 +295,16 @@ void run_typed_group(Context* cl, const std::vector<BatchImage>& imgs, const std
 // src/interface.c:20-94, as GPU producers hold it): the mixed call over the
 // images whose descriptor (view_ok) and boxes are valid, a single size group
 // split as a same-size batch.  A bad view or bad boxes fail their image alone
-// (the last message stays).  d_labels (or NULL): image i's palette label map
-// goes to d_labels[i] (NULL entries allowed), as in
-// phd_report_batch_device_mixed_labels: an 8-bit image's from its run's label
-// launch (ReportRun::label_maps), an fp64 image's from k_planar_labels.
+// (the last message stays).  outs: what the call returns per image beside the
+// report (CallOutputs, phd_host.h) -- an 8-bit image's from its run
+// (ReportRun), an fp64 image's from report_planes_device.
 template <class View, class Why>
-int report_views(const char* entry, BatchImage::Source kind, GroupFn run_group, const View* views, int n_images,
-                 const phd_config* cfg, const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
-                 Full_Report_Data** out, int* status, void* stream, Why view_ok,
-                 phd_box_palette* box_palettes = nullptr, phd_box_stats* box_stats = nullptr) {
-    clear_error();
-    if (box_palettes && n_images > 0)
-        for (int i = 0; i < n_images; i++) box_palettes[i] = phd_box_palette{0, 0, nullptr};
-    if (box_stats && n_images > 0)
-        for (int i = 0; i < n_images; i++) box_stats[i] = phd_box_stats{0, nullptr, nullptr};
-    if (!views || !cfg || !out || !status || n_images <= 0) {
-        set_error(std::string(entry) + ": bad arguments");
+int report_views(const char* family, BatchImage::Source kind, GroupFn run_group, const View* views, int n_images,
+                 const phd_config* cfg, const Crop_Boundaries* const* crops, const CallOutputs& outs,
+                 Full_Report_Data** out, int* status, void* stream, Why view_ok) {
+    if (!report_prologue(entry_name(family, "", outs), views && cfg && out && status && n_images > 0, n_images, cfg,
+                         outs))
         return -1;
-    }
-    // a label is a palette slot below PHD_LABEL_NONE's sign bit (int16 readers)
-    if ((d_labels || box_palettes) && make_grid(*cfg).tl >= 32768) {
-        set_error(std::string(entry) + ": label maps need fewer than 32768 octree groups (palette slots)");
-        return -1;
-    }
     std::vector<BatchImage> imgs;
     std::string bad;
     for (int i = 0; i < n_images; i++) {
@@ -314,8 +313,7 @@ int report_views(const char* entry, BatchImage::Source kind, GroupFn run_group, 
         std::string why;
         if (view_ok(views[i], &why) && (!crops || crops_why(crops[i], views[i].height, views[i].width, &why)))
             imgs.push_back({i, kind, &views[i], views[i].height, views[i].width, crops ? crops[i] : nullptr,
-                            d_labels ? d_labels[i] : nullptr, box_palettes ? box_palettes + i : nullptr,
-                            box_stats ? box_stats + i : nullptr});
+                            outs.of(i)});
         else bad = "image " + std::to_string(i) + ": " + why;
     }
     Context* c = get_context();
@@ -361,22 +359,59 @@ int convert_views(const char* entry, const View* views, int n_images, Dst* const
     return 0;
 }
 
-}  // namespace
-
-// Device images as byte-strided views, in the layouts GPU producers emit
-// (pack_view.h).  Each report entry below is its _labels entry with no maps.
-extern "C" int phd_report_batch_device_views_labels(const phd_image_view* views, int n_images, const phd_config* cfg,
-                                                    const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
-                                                    Full_Report_Data** out, int* status, void* stream) {
-    return report_views(d_labels ? "phd_report_batch_device_views_labels" : "phd_report_batch_device_views",
-                        BatchImage::kView, run_staged_group, views, n_images, cfg, crops, d_labels, out, status,
-                        stream, view_why);
+// The three families' bodies: every report entry below is one call of its own.
+int report_image_views(const phd_image_view* views, int n, const phd_config* cfg, const Crop_Boundaries* const* crops,
+                       const CallOutputs& outs, Full_Report_Data** out, int* status, void* stream) {
+    return report_views("views", BatchImage::kView, run_staged_group, views, n, cfg, crops, outs, out, status, stream,
+                        view_why);
 }
 
+int report_yuv_views(const phd_yuv_view* views, int n, const phd_config* cfg, const Crop_Boundaries* const* crops,
+                     const CallOutputs& outs, Full_Report_Data** out, int* status, void* stream) {
+    return report_views("yuv", BatchImage::kYuv, run_staged_group, views, n, cfg, crops, outs, out, status, stream,
+                        yuv_view_why);
+}
+
+int report_typed_views(const phd_typed_view* views, int n, const phd_config* cfg, const Crop_Boundaries* const* crops,
+                       const CallOutputs& outs, Full_Report_Data** out, int* status, void* stream) {
+    return report_views("typed_views", BatchImage::kTyped, run_typed_group, views, n, cfg, crops, outs, out, status,
+                        stream, typed_view_why);
+}
+
+}  // namespace
+
+// Each family has four report entries: the plain one, and with each image's
+// palette label map (_labels), its box palette too (_box_palettes: per crop
+// box, the elements of every palette slot) and its box statistics too
+// (_box_stats: per crop box, get_rgb_statistics and get_hsv_average of its
+// pixels).  An output passed as NULL is one the entry does not take.
+//
+// Device images as byte-strided views, in the layouts GPU producers emit (pack_view.h).
 extern "C" int phd_report_batch_device_views(const phd_image_view* views, int n_images, const phd_config* cfg,
                                              const Crop_Boundaries* const* crops, Full_Report_Data** out,
                                              int* status, void* stream) {
-    return phd_report_batch_device_views_labels(views, n_images, cfg, crops, nullptr, out, status, stream);
+    return report_image_views(views, n_images, cfg, crops, {}, out, status, stream);
+}
+
+extern "C" int phd_report_batch_device_views_labels(const phd_image_view* views, int n_images, const phd_config* cfg,
+                                                    const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
+                                                    Full_Report_Data** out, int* status, void* stream) {
+    return report_image_views(views, n_images, cfg, crops, {d_labels}, out, status, stream);
+}
+
+extern "C" int phd_report_batch_device_views_box_palettes(const phd_image_view* views, int n_images,
+                                                          const phd_config* cfg, const Crop_Boundaries* const* crops,
+                                                          uint16_t* const* d_labels, phd_box_palette* box_palettes,
+                                                          Full_Report_Data** out, int* status, void* stream) {
+    return report_image_views(views, n_images, cfg, crops, {d_labels, box_palettes}, out, status, stream);
+}
+
+extern "C" int phd_report_batch_device_views_box_stats(const phd_image_view* views, int n_images,
+                                                       const phd_config* cfg, const Crop_Boundaries* const* crops,
+                                                       uint16_t* const* d_labels, phd_box_palette* box_palettes,
+                                                       phd_box_stats* box_stats, Full_Report_Data** out, int* status,
+                                                       void* stream) {
+    return report_image_views(views, n_images, cfg, crops, {d_labels, box_palettes, box_stats}, out, status, stream);
 }
 
 extern "C" int phd_pack_views_device(const phd_image_view* views, int n_images, uint8_t* const* d_dst, void* stream) {
@@ -385,18 +420,30 @@ extern "C" int phd_pack_views_device(const phd_image_view* views, int n_images, 
 }
 
 // Device YCbCr frames as decoders emit them (yuv_view.h).
-extern "C" int phd_report_batch_device_yuv_labels(const phd_yuv_view* views, int n_images, const phd_config* cfg,
-                                                  const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
-                                                  Full_Report_Data** out, int* status, void* stream) {
-    return report_views(d_labels ? "phd_report_batch_device_yuv_labels" : "phd_report_batch_device_yuv",
-                        BatchImage::kYuv, run_staged_group, views, n_images, cfg, crops, d_labels, out, status, stream,
-                        yuv_view_why);
-}
-
 extern "C" int phd_report_batch_device_yuv(const phd_yuv_view* views, int n_images, const phd_config* cfg,
                                            const Crop_Boundaries* const* crops, Full_Report_Data** out, int* status,
                                            void* stream) {
-    return phd_report_batch_device_yuv_labels(views, n_images, cfg, crops, nullptr, out, status, stream);
+    return report_yuv_views(views, n_images, cfg, crops, {}, out, status, stream);
+}
+
+extern "C" int phd_report_batch_device_yuv_labels(const phd_yuv_view* views, int n_images, const phd_config* cfg,
+                                                  const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
+                                                  Full_Report_Data** out, int* status, void* stream) {
+    return report_yuv_views(views, n_images, cfg, crops, {d_labels}, out, status, stream);
+}
+
+extern "C" int phd_report_batch_device_yuv_box_palettes(const phd_yuv_view* views, int n_images, const phd_config* cfg,
+                                                        const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
+                                                        phd_box_palette* box_palettes, Full_Report_Data** out,
+                                                        int* status, void* stream) {
+    return report_yuv_views(views, n_images, cfg, crops, {d_labels, box_palettes}, out, status, stream);
+}
+
+extern "C" int phd_report_batch_device_yuv_box_stats(const phd_yuv_view* views, int n_images, const phd_config* cfg,
+                                                     const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
+                                                     phd_box_palette* box_palettes, phd_box_stats* box_stats,
+                                                     Full_Report_Data** out, int* status, void* stream) {
+    return report_yuv_views(views, n_images, cfg, crops, {d_labels, box_palettes, box_stats}, out, status, stream);
 }
 
 extern "C" int phd_convert_yuv_device(const phd_yuv_view* views, int n_images, uint8_t* const* d_dst, void* stream) {
@@ -405,43 +452,17 @@ extern "C" int phd_convert_yuv_device(const phd_yuv_view* views, int n_images, u
 }
 
 // Device images of any element type, as the reference's Pixels (src/types.h:5).
+extern "C" int phd_report_batch_device_typed_views(const phd_typed_view* views, int n_images, const phd_config* cfg,
+                                                   const Crop_Boundaries* const* crops, Full_Report_Data** out,
+                                                   int* status, void* stream) {
+    return report_typed_views(views, n_images, cfg, crops, {}, out, status, stream);
+}
+
 extern "C" int phd_report_batch_device_typed_views_labels(const phd_typed_view* views, int n_images,
                                                           const phd_config* cfg, const Crop_Boundaries* const* crops,
                                                           uint16_t* const* d_labels, Full_Report_Data** out,
                                                           int* status, void* stream) {
-    return report_views(d_labels ? "phd_report_batch_device_typed_views_labels"
-                                 : "phd_report_batch_device_typed_views",
-                        BatchImage::kTyped, run_typed_group, views, n_images, cfg, crops, d_labels, out, status,
-                        stream, typed_view_why);
-}
-
-extern "C" int phd_report_batch_device_typed_views(const phd_typed_view* views, int n_images, const phd_config* cfg,
-                                                   const Crop_Boundaries* const* crops, Full_Report_Data** out,
-                                                   int* status, void* stream) {
-    return phd_report_batch_device_typed_views_labels(views, n_images, cfg, crops, nullptr, out, status, stream);
-}
-
-// The three _labels entries plus each image's box palette (per crop box, the
-// elements of every palette slot: ReportRun::label_maps, report_planes_device).
-// box_palettes == NULL: exactly the _labels entry.
-extern "C" int phd_report_batch_device_views_box_palettes(const phd_image_view* views, int n_images,
-                                                          const phd_config* cfg, const Crop_Boundaries* const* crops,
-                                                          uint16_t* const* d_labels, phd_box_palette* box_palettes,
-                                                          Full_Report_Data** out, int* status, void* stream) {
-    if (!box_palettes)
-        return phd_report_batch_device_views_labels(views, n_images, cfg, crops, d_labels, out, status, stream);
-    return report_views("phd_report_batch_device_views_box_palettes", BatchImage::kView, run_staged_group, views,
-                        n_images, cfg, crops, d_labels, out, status, stream, view_why, box_palettes);
-}
-
-extern "C" int phd_report_batch_device_yuv_box_palettes(const phd_yuv_view* views, int n_images, const phd_config* cfg,
-                                                        const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
-                                                        phd_box_palette* box_palettes, Full_Report_Data** out,
-                                                        int* status, void* stream) {
-    if (!box_palettes)
-        return phd_report_batch_device_yuv_labels(views, n_images, cfg, crops, d_labels, out, status, stream);
-    return report_views("phd_report_batch_device_yuv_box_palettes", BatchImage::kYuv, run_staged_group, views,
-                        n_images, cfg, crops, d_labels, out, status, stream, yuv_view_why, box_palettes);
+    return report_typed_views(views, n_images, cfg, crops, {d_labels}, out, status, stream);
 }
 
 extern "C" int phd_report_batch_device_typed_views_box_palettes(const phd_typed_view* views, int n_images,
@@ -450,37 +471,7 @@ extern "C" int phd_report_batch_device_typed_views_box_palettes(const phd_typed_
                                                                 uint16_t* const* d_labels,
                                                                 phd_box_palette* box_palettes, Full_Report_Data** out,
                                                                 int* status, void* stream) {
-    if (!box_palettes)
-        return phd_report_batch_device_typed_views_labels(views, n_images, cfg, crops, d_labels, out, status, stream);
-    return report_views("phd_report_batch_device_typed_views_box_palettes", BatchImage::kTyped, run_typed_group, views,
-                        n_images, cfg, crops, d_labels, out, status, stream, typed_view_why, box_palettes);
-}
-
-// The three _box_palettes entries plus each image's box statistics (per crop
-// box, get_rgb_statistics and get_hsv_average of its pixels:
-// ReportRun::box_stat_job on the staged RGB8 images, report_planes_device on the
-// fp64 route).  box_stats == NULL: exactly the _box_palettes entry.
-extern "C" int phd_report_batch_device_views_box_stats(const phd_image_view* views, int n_images,
-                                                       const phd_config* cfg, const Crop_Boundaries* const* crops,
-                                                       uint16_t* const* d_labels, phd_box_palette* box_palettes,
-                                                       phd_box_stats* box_stats, Full_Report_Data** out, int* status,
-                                                       void* stream) {
-    if (!box_stats)
-        return phd_report_batch_device_views_box_palettes(views, n_images, cfg, crops, d_labels, box_palettes, out,
-                                                          status, stream);
-    return report_views("phd_report_batch_device_views_box_stats", BatchImage::kView, run_staged_group, views,
-                        n_images, cfg, crops, d_labels, out, status, stream, view_why, box_palettes, box_stats);
-}
-
-extern "C" int phd_report_batch_device_yuv_box_stats(const phd_yuv_view* views, int n_images, const phd_config* cfg,
-                                                     const Crop_Boundaries* const* crops, uint16_t* const* d_labels,
-                                                     phd_box_palette* box_palettes, phd_box_stats* box_stats,
-                                                     Full_Report_Data** out, int* status, void* stream) {
-    if (!box_stats)
-        return phd_report_batch_device_yuv_box_palettes(views, n_images, cfg, crops, d_labels, box_palettes, out,
-                                                        status, stream);
-    return report_views("phd_report_batch_device_yuv_box_stats", BatchImage::kYuv, run_staged_group, views, n_images,
-                        cfg, crops, d_labels, out, status, stream, yuv_view_why, box_palettes, box_stats);
+    return report_typed_views(views, n_images, cfg, crops, {d_labels, box_palettes}, out, status, stream);
 }
 
 extern "C" int phd_report_batch_device_typed_views_box_stats(const phd_typed_view* views, int n_images,
@@ -489,11 +480,7 @@ extern "C" int phd_report_batch_device_typed_views_box_stats(const phd_typed_vie
                                                              uint16_t* const* d_labels, phd_box_palette* box_palettes,
                                                              phd_box_stats* box_stats, Full_Report_Data** out,
                                                              int* status, void* stream) {
-    if (!box_stats)
-        return phd_report_batch_device_typed_views_box_palettes(views, n_images, cfg, crops, d_labels, box_palettes,
-                                                                out, status, stream);
-    return report_views("phd_report_batch_device_typed_views_box_stats", BatchImage::kTyped, run_typed_group, views,
-                        n_images, cfg, crops, d_labels, out, status, stream, typed_view_why, box_palettes, box_stats);
+    return report_typed_views(views, n_images, cfg, crops, {d_labels, box_palettes, box_stats}, out, status, stream);
 }
 
 // (one decode launch per image)

@@ -2,6 +2,8 @@
 // label map (the maps themselves: ReportRun::label_maps, phd_report.cpp).
 // Kernels: palette_labels.hip.
 
+#include <cstring>
+
 #include "phd_host.h"
 
 using namespace phd;
@@ -35,11 +37,12 @@ extern "C" int phd_labels_to_rgb_device(const uint16_t* const* d_labels, const i
     std::lock_guard<std::mutex> lk(c->mu);
     const hipStream_t st = work_stream(c, stream);
     const size_t rec_bytes = al(sizeof(LabelRgbRec) * (size_t)n_maps), bytes = rec_bytes + 4 * lut_words;
-    std::vector<uint8_t> tab(bytes);
-    LabelRgbRec* recs = reinterpret_cast<LabelRgbRec*>(tab.data());
-    unsigned* words = reinterpret_cast<unsigned*>(tab.data() + rec_bytes);
-    // the device table may move when it grows: size it before taking addresses
-    if (!ensure_device(&c->d_views, &c->views_bytes, bytes)) return -1;
+    // filled in the pinned block (the device table has its final address by then: the records point into it)
+    uint8_t* tab = (uint8_t*)table_begin(c, bytes);
+    if (!tab) return -1;
+    memset(tab, 0, rec_bytes);
+    LabelRgbRec* recs = reinterpret_cast<LabelRgbRec*>(tab);
+    unsigned* words = reinterpret_cast<unsigned*>(tab + rec_bytes);
     const unsigned* d_words = reinterpret_cast<const unsigned*>((const uint8_t*)c->d_views + rec_bytes);
     const unsigned none = (unsigned)none_rgb[0] | (unsigned)none_rgb[1] << 8 | (unsigned)none_rgb[2] << 16;
     long max_npix = 0;
@@ -53,7 +56,7 @@ extern "C" int phd_labels_to_rgb_device(const uint16_t* const* d_labels, const i
                          (unsigned)luts[i][3 * k + 2] << 16;
     }
     auto run = [&]() {
-        if (!upload_table(c, tab.data(), bytes, bytes, st)) return false;
+        if (!table_upload(c, bytes, st)) return false;
         PHD_HIP(launch_labels_to_rgb((const LabelRgbRec*)c->d_views, n_maps, max_npix, st));
         if (!table_launched(c, st)) return false;
         if (!stream) PHD_HIP(hipStreamSynchronize(st));

@@ -104,7 +104,7 @@ Full_Report_Data* report_planar(Context* c, const double* r, const double* g, co
         (void)hipStreamSynchronize(c->stream);
         return out;
     }
-    Full_Report_Data* out = report_planes_device(c, P, height, width, cfg, crops, st, nullptr);
+    Full_Report_Data* out = report_planes_device(c, P, height, width, cfg, crops, st, ImageOutputs{});
     (void)hipStreamSynchronize(st);
     c->prof.collect();                                      // (k_planar_sums' events, when profiled)
     return out;
@@ -114,14 +114,12 @@ Full_Report_Data* report_planar(Context* c, const double* r, const double* g, co
 // the device already -- P.r | P.g | P.b are the first 3 n doubles of
 // c->d_planes (4 n doubles), whose fourth plane takes the luma.  cfg, the size
 // and the boxes are validated; nothing but the planes' own producer is queued
-// on st (no buffer allocated here is in use).  labels (or NULL): the image's
-// palette label map (device, (height / ds) x (width / ds) uint16), written on
-// st behind the palette tail and complete when the call returns; untouched when
-// the image fails before its palette decision.
+// on st (no buffer allocated here is in use).  outs (ImageOutputs, phd_host.h):
+// the label map is written on st behind the palette tail.
 Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int height, int width, const phd_config& cfg,
-                                       const Crop_Boundaries* crops, hipStream_t st, uint16_t* labels,
-                                       phd_box_palette* box_pal, phd_box_stats* box_stats) {
+                                       const Crop_Boundaries* crops, hipStream_t st, const ImageOutputs& outs) {
     std::string why;
+    uint16_t* labels = outs.labels;                          // (or a scratch map for the box counts)
     const long n = (long)height * width;
     double* pgm = c->d_planes + 3 * n;
     const int nb = planar_blocks(n);
@@ -142,7 +140,7 @@ Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int heigh
         !ensure_device((void**)&c->d_inter, &c->inter_bytes, sizeof(double2) * ((size_t)height * wf + 1024)))
         return nullptr;
     // box palettes: the boxes are counted from the caller's map, or from one in the context's scratch
-    const bool count_boxes = box_pal && ncrops > 0;
+    const bool count_boxes = outs.box_pal && ncrops > 0;
     const int mh = ds > 1 ? height / ds : height, mw = ds > 1 ? width / ds : width;
     if (count_boxes && !labels) {
         if (!ensure_device(&c->d_labscratch, &c->labscratch_bytes, sizeof(uint16_t) * (size_t)mh * mw)) return nullptr;
@@ -152,7 +150,7 @@ Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int heigh
     // pinned: the items going up, then the two partial arrays coming down
     std::vector<PlanarBoxItem> bs_items;
     size_t bs_o1 = 0, bs_o2 = 0;
-    if (box_stats && ncrops > 0) {
+    if (outs.box_stats && ncrops > 0) {
         std::vector<BoxItem> bands;
         for (int k = 0; k < ncrops; k++) {
             const int first = (int)bands.size(), cols = crops->right[k] - crops->left[k];
@@ -297,8 +295,9 @@ Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int heigh
                                      (const unsigned long long*)(h.data() + R.bins), fmax, cfg, crops,
                                      (const double*)(h.data() + R.sharp), &why, bscale);
     if (!out) set_error(why);
-    else if (box_pal) (void)box_palette_fill(box_pal, ncrops, (int)dec.parents.size(), (const uint32_t*)c->h_boxpal);
-    if (out && !bs_items.empty() && box_stats_alloc(box_stats, ncrops)) {
+    else if (outs.box_pal)
+        (void)box_palette_fill(outs.box_pal, ncrops, (int)dec.parents.size(), (const uint32_t*)c->h_boxpal);
+    if (out && !bs_items.empty() && box_stats_alloc(outs.box_stats, ncrops)) {
         // the items' partials in item order: B = sum / N as the device formed it,
         // C = sqrt(sum (x - B)^2 / N), S-bar = sum(s) / N
         const double* p1 = (const double*)c->h_boxstat;
@@ -312,12 +311,12 @@ Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int heigh
                 for (int ch = 0; ch < 3; ch++) a2[ch] += p2[3 * j + ch];
             }
             const double nn = (double)it.npix;
-            double* sb = &box_stats->stats[box].Br;
+            double* sb = &outs.box_stats->stats[box].Br;
             for (int ch = 0; ch < 3; ch++) {
                 sb[ch] = a1[ch] / nn;
                 sb[3 + ch] = std::sqrt(a2[ch] / nn);
             }
-            box_stats->average_saturation[box] = a1[3] / nn;
+            outs.box_stats->average_saturation[box] = a1[3] / nn;
         }
     }
     return out;

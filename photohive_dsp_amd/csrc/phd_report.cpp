@@ -361,9 +361,7 @@ struct ReportArgs {
     int* status;
     hipStream_t stream;
     const Crop_Boundaries* const* img_crops;
-    uint16_t* const* labels;                                  // per-image label maps (device) or NULL
-    phd_box_palette* const* box_pal;                          // per-image box palettes (host structs) or NULL
-    phd_box_stats* const* box_stats;                          // per-image box statistics (host structs) or NULL
+    const ImageOutputs* outs;                                 // per image (phd_host.h), or NULL: none
 };
 
 // How a call's FFT chain is launched: a row and a column launch per image, or
@@ -408,19 +406,27 @@ struct ReportRun : ReportArgs {
     uint8_t* hc() const { return hp + (size_t)n * L.a_bytes; }   // the C records on the host
 
     bool plan(), k1(), fft_chain(), palette_tail(), downloads(), assemble_groups(), timings();
+    // image i's outputs; whether any image of the run asks for the output m
+    ImageOutputs o(int i) const { return outs ? outs[i] : ImageOutputs{}; }
+    template <class T>
+    bool any(T ImageOutputs::*m) const {
+        for (int i = 0; i < n; i++)
+            if (o(i).*m) return true;
+        return false;
+    }
     bool label_maps();                                        // palette_tail()'s last step: maps and box counts
     bool label_launches(const std::vector<LabelDst>& dst, bool aligned);
     // box palettes: image i's boxes are counted (it has a decision, a struct
     // and boxes); where its counters start in Context::h_boxpal (-1: none)
     bool counts_boxes(int i) const {
-        return box_pal && box_pal[i] && ok[i] && img_crops && img_crops[i] && img_crops[i]->N > 0;
+        return o(i).box_pal && ok[i] && img_crops && img_crops[i] && img_crops[i]->N > 0;
     }
     std::vector<long long> bp_off;
     bool box_palettes();                                      // the last stage: the structs of the reported images
     // box statistics: image i's boxes are summed (it has a struct and boxes);
     // where its boxes start in the job's download (-1: none)
     bool sums_boxes(int i) const {
-        return box_stats && box_stats[i] && img_crops && img_crops[i] && img_crops[i]->N > 0;
+        return o(i).box_stats && img_crops && img_crops[i] && img_crops[i]->N > 0;
     }
     std::vector<long long> bs_off;
     bool box_stat_job();                                      // fft_chain()'s first step, with the sharpness launch
@@ -584,7 +590,7 @@ bool ReportRun::fft_chain() {
     if (img_crops && !enqueue_sharpness(c, d_imgs, n, width, splan, (double*)(dw + L.C(n, 0) + L.c_sharp),
                                         (long)(L.c_bytes / 8), sf))
         return false;
-    if (box_stats && !box_stat_job()) return false;
+    if (any(&ImageOutputs::box_stats) && !box_stat_job()) return false;
     const uint8_t* const* d_ptrs = (const uint8_t* const*)(dw + L.P_dev(n));
     const long a_stride = (long)(L.a_bytes / 8), c_stride = (long)(L.c_bytes / 8);
     for (int g0 = 0; g0 < n; g0 += Q) {
@@ -722,7 +728,7 @@ bool ReportRun::palette_tail() {
     if (!launch_palette_tail(c, L, n, d_imgs, height, width, ds, gp, cls, nchunks, fused, dec.data(), ok.data(), n_ent,
                              max_slots, max_per_img, s2))
         return false;
-    if ((labels || box_pal) && !label_maps()) return false;
+    if ((any(&ImageOutputs::labels) || any(&ImageOutputs::box_pal)) && !label_maps()) return false;
     PHD_HIP(hipEventRecord(c->ev_tail, s2));
     return true;
 }
@@ -745,7 +751,7 @@ bool ReportRun::label_maps() {
     const size_t one = al(sizeof(uint16_t) * (size_t)mh * mw);
     size_t scratch = 0;
     for (int i = 0; i < n; i++) {
-        if (labels && ok[i]) map[i] = labels[i];
+        if (ok[i]) map[i] = o(i).labels;
         if (!map[i] && counts_boxes(i)) scratch += one;
     }
     if (scratch) {
@@ -766,7 +772,6 @@ bool ReportRun::label_maps() {
     }
     if (dst.empty()) return true;
     if (!label_launches(dst, aligned)) return false;
-    if (!box_pal) return true;
     BoxJob job;
     bp_off.assign(n, -1);
     for (int i = 0; i < n; i++) {
@@ -923,11 +928,10 @@ bool ReportRun::timings() {
 // for each, the counts where the image has boxes.  A failed image keeps
 // {0, 0, NULL}.
 bool ReportRun::box_palettes() {
-    if (!box_pal) return true;
     for (int i = 0; i < n; i++) {
-        if (!box_pal[i] || !out[i]) continue;
+        if (!o(i).box_pal || !out[i]) continue;
         const bool counted = counts_boxes(i) && !bp_off.empty() && bp_off[i] >= 0;
-        if (!box_palette_fill(box_pal[i], counted ? img_crops[i]->N : 0, (int)c->dec_scratch[i].parents.size(),
+        if (!box_palette_fill(o(i).box_pal, counted ? img_crops[i]->N : 0, (int)c->dec_scratch[i].parents.size(),
                               counted ? (const uint32_t*)c->h_boxpal + bp_off[i] : nullptr))
             return false;
     }
@@ -938,10 +942,9 @@ bool ReportRun::box_palettes() {
 // box_stat_job's download left in Context::h_boxstat (timings() has waited for
 // it).  A failed image and an image without boxes keep {0, NULL, NULL}.
 bool ReportRun::box_statistics() {
-    if (!box_stats) return true;
     for (int i = 0; i < n; i++) {
         if (!out[i] || !sums_boxes(i) || bs_off.empty() || bs_off[i] < 0) continue;
-        if (!box_stats_fill(box_stats[i], img_crops[i], box_stats_host(c) + (size_t)bs_off[i] * kBoxStatOut))
+        if (!box_stats_fill(o(i).box_stats, img_crops[i], box_stats_host(c) + (size_t)bs_off[i] * kBoxStatOut))
             return false;
     }
     return true;
@@ -951,10 +954,8 @@ bool ReportRun::box_statistics() {
 
 bool run_reports(Context* c, const uint8_t* const* d_imgs, int n, int height, int width,
                  const phd_config& cfg, const Crop_Boundaries* crops, Full_Report_Data** out, int* status,
-                 hipStream_t stream, const Crop_Boundaries* const* img_crops, uint16_t* const* labels,
-                 phd_box_palette* const* box_pal, phd_box_stats* const* box_stats) {
-    ReportRun r(ReportArgs{c, d_imgs, n, height, width, cfg, crops, out, status, stream, img_crops, labels, box_pal,
-                           box_stats});
+                 hipStream_t stream, const Crop_Boundaries* const* img_crops, const ImageOutputs* outs) {
+    ReportRun r(ReportArgs{c, d_imgs, n, height, width, cfg, crops, out, status, stream, img_crops, outs});
     return r.plan() && r.k1() && r.fft_chain() && r.palette_tail() && r.downloads() && r.assemble_groups() &&
            r.timings() && r.box_palettes() && r.box_statistics() && r.failures == 0;
 }

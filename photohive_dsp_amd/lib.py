@@ -140,10 +140,35 @@ lib.free_full_report.argtypes = [P(P(Full_Report_Data))]
 lib.phd_free_reports.restype = None
 lib.phd_free_reports.argtypes = [P(P(Full_Report_Data)), ctypes.c_int]
 lib.phd_free_pgm.argtypes = [P(Image_PGM)]
+
+
+def _report_prototypes():
+    """The sixteen report entries over device images of any sizes: four families,
+    told apart by their leading arguments (packed images: n pointers, heights
+    and widths; views, typed views, YUV views: n descriptors), times what an
+    entry can return per image after the crop boxes (crops: n pointers to
+    Crop_Boundaries) -- nothing, `labels` (n device pointers to uint16 maps),
+    `box_palettes` (n PhdBoxPalette) after them, `box_stats` (n PhdBoxStats)
+    after those."""
+    v, i = ctypes.c_void_p, ctypes.c_int
+    results = [P(P(Full_Report_Data)), P(i)]
+    families = (("mixed", "mixed_crops", [v, v, v, i], [v, v]),
+                ("views", "views", [P(PhdImageView), i], results),
+                ("typed_views", "typed_views", [P(PhdTypedView), i], results),
+                ("yuv", "yuv", [P(PhdYuvView), i], results))
+    outputs = (("", []), ("_labels", [v]), ("_box_palettes", [v, P(PhdBoxPalette)]),
+               ("_box_stats", [v, P(PhdBoxPalette), P(PhdBoxStats)]))
+    for family, plain, head, out_status in families:
+        for suffix, tail in outputs:
+            yield ("phd_report_batch_device_" + (family + suffix if suffix else plain), i,
+                   head + [P(PhdConfig), P(P(Crop_Boundaries))] + tail + out_status + [v])
+
+
 # round-6 and later entry points, bound only when present: an A/B timing run may load an
 # older build through PHD_LIB (tools/); the shipped library exports all of them
 # (tests/test_abi.py checks every symbol of include/photohive_dsp.h)
-for _name, _res, _args in (("phd_shutdown", None, []),
+for _name, _res, _args in (*_report_prototypes(),
+                           ("phd_shutdown", None, []),
                            ("phd_debug_fft_split_pass", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
                            ("phd_install_crash_maps", ctypes.c_int, [ctypes.c_char_p]),
                            ("phd_debug_library_threads", ctypes.c_int, [ctypes.c_int]),
@@ -154,9 +179,6 @@ for _name, _res, _args in (("phd_shutdown", None, []),
                             [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_size_t,
                              P(PhdConfig), P(P(Crop_Boundaries)), P(P(Full_Report_Data)), P(ctypes.c_int),
                              ctypes.c_void_p]),
-                           ("phd_report_batch_device_mixed_crops", ctypes.c_int,
-                            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, P(PhdConfig),
-                             P(P(Crop_Boundaries)), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
                            ("phd_report_batch_u8_crops", ctypes.c_int,
                             [P(ctypes.c_void_p), P(ctypes.c_int), P(ctypes.c_int), ctypes.c_int, P(PhdConfig),
                              P(P(Crop_Boundaries)), P(P(Full_Report_Data)), P(ctypes.c_int)]),
@@ -167,42 +189,18 @@ for _name, _res, _args in (("phd_shutdown", None, []),
                             [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, P(Crop_Boundaries),
                              P(ctypes.c_double)]),
                            # device images as byte-strided views (views: n PhdImageView)
-                           ("phd_report_batch_device_views", ctypes.c_int,
-                            [P(PhdImageView), ctypes.c_int, P(PhdConfig), P(P(Crop_Boundaries)),
-                             P(P(Full_Report_Data)), P(ctypes.c_int), ctypes.c_void_p]),
                            ("phd_pack_views_device", ctypes.c_int,
                             [P(PhdImageView), ctypes.c_int, P(ctypes.c_void_p), ctypes.c_void_p]),
                            ("phd_debug_pack_view_host", ctypes.c_int, [P(PhdImageView), ctypes.c_void_p]),
                            # device images of any element type (views: n PhdTypedView)
-                           ("phd_report_batch_device_typed_views", ctypes.c_int,
-                            [P(PhdTypedView), ctypes.c_int, P(PhdConfig), P(P(Crop_Boundaries)),
-                             P(P(Full_Report_Data)), P(ctypes.c_int), ctypes.c_void_p]),
                            ("phd_decode_views_device", ctypes.c_int,
                             [P(PhdTypedView), ctypes.c_int, P(ctypes.c_void_p), ctypes.c_void_p]),
                            ("phd_debug_decode_view_host", ctypes.c_int,
                             [P(PhdTypedView), ctypes.c_void_p, ctypes.c_void_p, P(ctypes.c_int)]),
                            # device YCbCr frames (views: n PhdYuvView)
-                           ("phd_report_batch_device_yuv", ctypes.c_int,
-                            [P(PhdYuvView), ctypes.c_int, P(PhdConfig), P(P(Crop_Boundaries)),
-                             P(P(Full_Report_Data)), P(ctypes.c_int), ctypes.c_void_p]),
                            ("phd_convert_yuv_device", ctypes.c_int,
                             [P(PhdYuvView), ctypes.c_int, P(ctypes.c_void_p), ctypes.c_void_p]),
                            ("phd_debug_yuv_view_host", ctypes.c_int, [P(PhdYuvView), ctypes.c_void_p]),
-                           # palette label maps (labels: n device pointers to uint16 maps)
-                           ("phd_report_batch_device_mixed_labels", ctypes.c_int,
-                            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, P(PhdConfig),
-                             P(P(Crop_Boundaries)), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                             ctypes.c_void_p]),
-                           # ... of views, typed views and YUV frames (the entries above plus `labels`)
-                           ("phd_report_batch_device_views_labels", ctypes.c_int,
-                            [P(PhdImageView), ctypes.c_int, P(PhdConfig), P(P(Crop_Boundaries)), ctypes.c_void_p,
-                             P(P(Full_Report_Data)), P(ctypes.c_int), ctypes.c_void_p]),
-                           ("phd_report_batch_device_typed_views_labels", ctypes.c_int,
-                            [P(PhdTypedView), ctypes.c_int, P(PhdConfig), P(P(Crop_Boundaries)), ctypes.c_void_p,
-                             P(P(Full_Report_Data)), P(ctypes.c_int), ctypes.c_void_p]),
-                           ("phd_report_batch_device_yuv_labels", ctypes.c_int,
-                            [P(PhdYuvView), ctypes.c_int, P(PhdConfig), P(P(Crop_Boundaries)), ctypes.c_void_p,
-                             P(P(Full_Report_Data)), P(ctypes.c_int), ctypes.c_void_p]),
                            ("phd_labels_to_rgb_device", ctypes.c_int,
                             [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
@@ -211,20 +209,6 @@ for _name, _res, _args in (("phd_shutdown", None, []),
                             [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                              P(P(Crop_Boundaries)), P(PhdBoxPalette), ctypes.c_void_p]),
                            ("phd_free_box_palettes", None, [P(PhdBoxPalette), ctypes.c_int]),
-                           # the four _labels entries plus `box_palettes` (n PhdBoxPalette) after `labels`
-                           ("phd_report_batch_device_mixed_box_palettes", ctypes.c_int,
-                            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, P(PhdConfig),
-                             P(P(Crop_Boundaries)), ctypes.c_void_p, P(PhdBoxPalette), ctypes.c_void_p,
-                             ctypes.c_void_p, ctypes.c_void_p]),
-                           ("phd_report_batch_device_views_box_palettes", ctypes.c_int,
-                            [P(PhdImageView), ctypes.c_int, P(PhdConfig), P(P(Crop_Boundaries)), ctypes.c_void_p,
-                             P(PhdBoxPalette), P(P(Full_Report_Data)), P(ctypes.c_int), ctypes.c_void_p]),
-                           ("phd_report_batch_device_typed_views_box_palettes", ctypes.c_int,
-                            [P(PhdTypedView), ctypes.c_int, P(PhdConfig), P(P(Crop_Boundaries)), ctypes.c_void_p,
-                             P(PhdBoxPalette), P(P(Full_Report_Data)), P(ctypes.c_int), ctypes.c_void_p]),
-                           ("phd_report_batch_device_yuv_box_palettes", ctypes.c_int,
-                            [P(PhdYuvView), ctypes.c_int, P(PhdConfig), P(P(Crop_Boundaries)), ctypes.c_void_p,
-                             P(PhdBoxPalette), P(P(Full_Report_Data)), P(ctypes.c_int), ctypes.c_void_p]),
                            ("phd_debug_box_counts_host", ctypes.c_int,
                             [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, P(Crop_Boundaries),
                              ctypes.c_void_p]),
@@ -233,23 +217,6 @@ for _name, _res, _args in (("phd_shutdown", None, []),
                             [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                              P(P(Crop_Boundaries)), P(PhdBoxStats), ctypes.c_void_p]),
                            ("phd_free_box_stats", None, [P(PhdBoxStats), ctypes.c_int]),
-                           # the four _box_palettes entries plus `box_stats` (n PhdBoxStats) after `box_palettes`
-                           ("phd_report_batch_device_mixed_box_stats", ctypes.c_int,
-                            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, P(PhdConfig),
-                             P(P(Crop_Boundaries)), ctypes.c_void_p, P(PhdBoxPalette), P(PhdBoxStats),
-                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-                           ("phd_report_batch_device_views_box_stats", ctypes.c_int,
-                            [P(PhdImageView), ctypes.c_int, P(PhdConfig), P(P(Crop_Boundaries)), ctypes.c_void_p,
-                             P(PhdBoxPalette), P(PhdBoxStats), P(P(Full_Report_Data)), P(ctypes.c_int),
-                             ctypes.c_void_p]),
-                           ("phd_report_batch_device_typed_views_box_stats", ctypes.c_int,
-                            [P(PhdTypedView), ctypes.c_int, P(PhdConfig), P(P(Crop_Boundaries)), ctypes.c_void_p,
-                             P(PhdBoxPalette), P(PhdBoxStats), P(P(Full_Report_Data)), P(ctypes.c_int),
-                             ctypes.c_void_p]),
-                           ("phd_report_batch_device_yuv_box_stats", ctypes.c_int,
-                            [P(PhdYuvView), ctypes.c_int, P(PhdConfig), P(P(Crop_Boundaries)), ctypes.c_void_p,
-                             P(PhdBoxPalette), P(PhdBoxStats), P(P(Full_Report_Data)), P(ctypes.c_int),
-                             ctypes.c_void_p]),
                            ("phd_debug_box_stats_host", ctypes.c_int,
                             [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, P(Crop_Boundaries), ctypes.c_void_p,
                              ctypes.c_void_p, ctypes.c_void_p]),

@@ -13,7 +13,8 @@ synchronised per box.
 2. In the call: images per second of phd_report_batch_device_mixed_box_stats
 (d_labels and box_palettes NULL) on 64 images of 4000 x 3000 with the 8
 face-sized boxes each, against phd_report_batch_device_mixed_crops, alternating,
-three runs each.  Prints one JSON line per figure."""
+three runs each.  BOX_BENCH_CALL_ONLY=1: part 2 alone (an A/B of two builds
+through PHD_LIB).  Prints one JSON line per figure."""
 import ctypes, json, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -59,7 +60,7 @@ ptrs = (ctypes.c_void_p * N)(*[imgs[i].data_ptr() for i in range(N)])
 hs, ws = (ctypes.c_int * N)(*[H] * N), (ctypes.c_int * N)(*[W] * N)
 
 # ---- 1. the kernel alone ----------------------------------------------------------------
-for name in SETS[0]:
+for name in ([] if os.environ.get("BOX_BENCH_CALL_ONLY") else SETS[0]):
     crops = normalize_salient([s[name] for s in SETS], N)
     pixels = sum((b["bottom"] - b["top"]) * (b["right"] - b["left"]) for s in SETS for b in s[name])
     boxes = sum(len(s[name]) for s in SETS)
