@@ -819,6 +819,78 @@ int phd_debug_window_vectors_host(const uint8_t* rgb, int height, int width, con
 int phd_debug_window_finish_host(const unsigned long long* bin_sums, double fft_max, int window,
                                  const phd_config* cfg, double* bins, Blur_Vector* vectors);
 
+/* ---- sharpness maps: the Laplacian sharpness of window grids, on the device ------
+ * The window sharpness of a T x T window (rows top <= y < top+T, columns
+ * left <= x < left+T, crop_pgm's convention, src/image_processing.c:213-232) is
+ * get_variance_sharpness (src/filtering.c:151-183) on that crop of the
+ * full-resolution luma.  The steps are rgb2pgm (src/image_processing.c:505-512),
+ * the 3x3 Laplacian with taps outside the crop skipped (filter_image,
+ * src/filtering.c:81-107), and then variance / average (get_average and
+ * get_variance, src/filtering.c:125-148).  downsample_rate plays no part.
+ *
+ * For 8-bit images every term is an integer, and the library keeps it so:
+ *  - l(y,x) = 299 R + 587 G + 114 B.  This is the reference's luma times 255000
+ *    and is at most 255000.
+ *  - f(y,x) = 9 l(y,x) - sum of l over the 3x3 neighbourhood inside the window.
+ *    Positions outside the window count as 0, so the centre weighs 8 and each
+ *    neighbour inside weighs -1.  |f| <= 2,040,000.
+ *  - n = T^2, S1 = sum f, S2 = sum f^2.  Only the window's border ring contributes
+ *    to S1, so S1 >= 0 and fits 32 bits.  S2 fits a u64.
+ *  - D = n S2 - S1^2.  It is never negative and exceeds 64 bits at T = 128; it is
+ *    kept as 128 bits (two u64 words).
+ *  - The finish is the only floating point.  It is shared by the kernel and the
+ *    host twin (sharp_window.h), plain IEEE fp64 operations with no fused
+ *    multiply-add:
+ *      num       = (double)hi * 18446744073709551616.0 + (double)lo
+ *      sharpness = num / (((double)n * (double)S1) * 255000.0)
+ *      variance  = num / (((double)n * (double)n) * 65025000000.0)
+ *  - S1 == 0 means the window's border ring is black.  The reference's average is
+ *    then 0.  The division above gives what IEEE gives: NaN when D == 0 (an
+ *    all-black window) and +inf otherwise.  It is left unguarded.
+ * Because the integer sums are exact, a window's values depend on its 3 T^2 bytes
+ * only.  They are bit-identical on every run and wherever the window sits in the
+ * call, and the kernel and its host twin agree bit for bit.
+ *
+ * window is 16, 32, 64 or 128; at 64 and 128 one window_grid serves the blur
+ * vector map and this map.  d_sharpness[i]: device pointer, 8-byte aligned,
+ * receives n_i doubles (n_i is windows[i]->N or gh * gw); it may be NULL only when
+ * n_i == 0.  d_variance is optional: NULL, or NULL entries, give no variances for
+ * those images; an entry is 8-byte aligned and receives n_i doubles.  Nothing is
+ * written outside those bytes.  Images are packed RGB8 device images of any sizes
+ * from T x T at any base alignment; no byte outside an image's 3 * H * W is read
+ * (rows are read as aligned dwords; the dwords that hold an image's first and
+ * last bytes are read byte by byte).
+ * Refused with -1 before any device work (also on a machine without a GPU),
+ * phd_last_error naming image and window: NULL arguments, a NULL image,
+ * n_images <= 0, a size below T, a window size outside the four, a box whose sides
+ * are not T or that leaves the image, a non-positive stride, a NULL d_sharpness
+ * entry of an image that has windows, more than 2^31 - 1 windows.
+ * One launch (profile slot 16) takes every window of every image: 256-thread
+ * blocks, one window per block at 128 and 64 and one per wave at 32 and 16, the
+ * window's luma in LDS as int32.  Per call one table upload (a 16-byte record and
+ * a destination pair per window) and no allocation.  Enqueued on `stream` and not
+ * waited for, or (NULL) on the library's stream and waited for, as
+ * phd_pack_views_device.  A call with no window at all does no device work and
+ * returns 0.  0 or -1. */
+/* Window lists, as phd_blur_vectors_device takes them. */
+int phd_sharpness_windows_device(const uint8_t* const* d_images, const int* heights, const int* widths,
+                                 int n_images, const Crop_Boundaries* const* windows, int window,
+                                 double* const* d_sharpness, double* const* d_variance, void* stream);
+/* A regular grid per image: window_grid's rule, gh = (H - T) / stride + 1, gw = (W - T) / stride + 1,
+ * row-major; stride > 0, may be smaller (overlap) or larger than the window. */
+int phd_sharpness_maps_device(const uint8_t* const* d_images, const int* heights, const int* widths, int n_images,
+                              int window, int stride, double* const* d_sharpness, double* const* d_variance,
+                              void* stream);
+/* Validation hook, host only (no GPU): the window sharpness kernel's twin
+ * (get_variance_sharpness, src/filtering.c:151-183, with filter_image, :81-107,
+ * get_average and get_variance, :125-148, on the crops of
+ * src/image_processing.c:213-232 after rgb2pgm, :505-512): the same row code and
+ * the same finish (sharp_window.h) over one packed RGB8 image of host memory at
+ * any alignment.  sharpness: windows->N doubles; variance: as many, or NULL; sums:
+ * S1, S2 per window (2 * windows->N), or NULL.  0, or -1 with phd_last_error. */
+int phd_debug_window_sharpness_host(const uint8_t* rgb, int height, int width, const Crop_Boundaries* windows,
+                                    int window, double* sharpness, double* variance, unsigned long long* sums);
+
 /* Palette intermediates of one device-resident image, for bit-exact checks:
  * hist[TL] (arm_octree quantities), parents[*n_parents] (valid_parents in
  * palette order), kept[*n_parents] (pixels surviving group_irregular_pixels).
@@ -930,7 +1002,7 @@ int phd_last_timings(double* ms, int n);
  * 1 fft_rows, 2 fft_cols, 3 palette_cutoffs, 4 palette_sums, 5 sharpness,
  * 6 pack_views, 7 classify_views, 8 decode_views, 9 yuv_views,
  * 10 palette_labels, 11 box_palettes, 12 box_stats, 13 the fp64 route's
- * planar_box_stats, 14 window_blur, 15 window_vectors).
+ * planar_box_stats, 14 window_blur, 15 window_vectors, 16 window_sharp).
  * phd_profile_kernels resets the counters; phd_profile_read returns the
  * accumulated milliseconds and launch count of one kernel. */
 int phd_profile_kernels(unsigned mask);

@@ -1079,6 +1079,73 @@ def blur_vector_maps_device(images, window=128, stride=None, stream=None, **kw):
     return _blur_vectors_call(images, [g[0] * g[1] for g in grids], grids, stream, call)
 
 
+def _sharpness_windows_call(images, counts, shapes, variance, stream, call):
+    """The device tensors of a window sharpness call and the call itself: per
+    image the sharpness shaped shapes[i], or (sharpness, variance)."""
+    import torch
+    n = len(images)
+    sharp = [torch.empty((c,), dtype=torch.float64, device=im.device) for im, c in zip(images, counts)]
+    var = [torch.empty((c,), dtype=torch.float64, device=im.device) for im, c in zip(images, counts)] if variance else []
+    if stream is not None:
+        for t in sharp + var:
+            t.record_stream(stream)
+    ptrs, hs, ws = _image_arrays(images)
+    ps = (ctypes.c_void_p * n)(*[s.data_ptr() if c else None for s, c in zip(sharp, counts)])
+    pv = (ctypes.c_void_p * n)(*[v.data_ptr() if c else None for v, c in zip(var, counts)]) if variance else None
+    call(ptrs, hs, ws, n, ps, pv, _stream_handle(stream))
+    sharp = [s.reshape(tuple(shp)) for s, shp in zip(sharp, shapes)]
+    if not variance:
+        return sharp
+    return [(s, v.reshape(tuple(shp))) for s, v, shp in zip(sharp, var, shapes)]
+
+
+def sharpness_windows_device(images, windows, window=64, variance=False, stream=None):
+    """The Laplacian sharpness of every window, left on the device
+    (phd_sharpness_windows_device): per image a float64 device tensor [n] -- the
+    reference's get_variance_sharpness on each window's crop of the
+    full-resolution luma -- or with variance=True a pair (sharpness, variance of
+    the Laplacian).  images: packed uint8 [H, W, 3] device tensors of any sizes
+    from window x window; windows: per image None, a Crop_Boundaries or a sequence
+    of (top, bottom, left, right) boxes whose sides are `window` (16, 32, 64 or
+    128).  A window with a black border ring gives +inf (NaN when it is black
+    throughout).  One launch takes every window of every image; nothing is copied
+    to the host; with stream= the call is enqueued on that stream and the tensors
+    are valid in its order."""
+    images = _packed_images(images, cuda=True)
+    n = len(images)
+    entries = _window_entries(windows, n)
+    if n == 0:
+        return []
+    arr, keep = _window_array(entries)
+    counts = [0 if cb is None else int(cb.N) for cb in keep]
+
+    def call(ptrs, hs, ws, n, ps, pv, s):
+        if lib.phd_sharpness_windows_device(ptrs, hs, ws, n, arr, int(window), ps, pv, s) != 0:
+            raise RuntimeError(f"sharpness_windows_device failed: {last_error()}")
+
+    return _sharpness_windows_call(images, counts, [(c,) for c in counts], variance, stream, call)
+
+
+def sharpness_maps_device(images, window=64, stride=None, variance=False, stream=None):
+    """sharpness_windows_device over window_grid of every image, the grid formed by
+    the library (phd_sharpness_maps_device): per image a float64 device tensor
+    [gh, gw], or with variance=True a pair of them.  At window 64 and 128 the grid
+    is blur_vector_maps_device's."""
+    images = _packed_images(images, cuda=True)
+    n = len(images)
+    stride = window if stride is None else int(stride)
+    if n == 0:
+        return []
+    grids = [window_grid(int(im.shape[0]), int(im.shape[1]), window, stride)[1] if stride > 0 and window > 0
+             else (0, 0) for im in images]
+
+    def call(ptrs, hs, ws, n, ps, pv, s):
+        if lib.phd_sharpness_maps_device(ptrs, hs, ws, n, int(window), stride, ps, pv, s) != 0:
+            raise RuntimeError(f"sharpness_maps_device failed: {last_error()}")
+
+    return _sharpness_windows_call(images, [g[0] * g[1] for g in grids], grids, variance, stream, call)
+
+
 def set_bounding_boxes(bounding_boxes):
     """core.py:489-515."""
     n = len(bounding_boxes)

@@ -334,6 +334,15 @@ void window_twiddles(int T, double2* tw);   // tw[e] = exp(-2 pi i e / T), e < T
 void window_bins_host(int T, const uint8_t* first, long long pitch, const uint16_t* binmap, int nbins,
                       unsigned long long* bins, double* fmax_out);
 
+// ---- window sharpness (window_sharp.hip; row code and finish: sharp_window.h) ------
+// Per T x T window (T = 16, 32, 64 or 128) of a packed RGB8 image its Laplacian
+// sharpness to d_dst[w].sharpness and the Laplacian's variance to
+// d_dst[w].variance (8-byte aligned; the variance or NULL): n windows, one launch.
+constexpr int kProfWindowSharp = 16;
+struct SharpWinRec;
+struct SharpWinDst;
+hipError_t launch_window_sharp(int T, const SharpWinRec* d_recs, const SharpWinDst* d_dst, int n, hipStream_t st);
+
 // Row pass: luma - avg of two rows as one complex sequence, FFT, split, write
 // the half spectra column-major into inter[wf][height].
 // Runtime-plan FFT passes over a batch of same-size images in one launch each
