@@ -1012,25 +1012,67 @@ def blur_map_device(images, window=128, stride=None, stream=None, **kw):
     return [tuple(a.reshape(g[1] + a.shape[1:]) for a in r) for r, g in zip(res, grids)]
 
 
-def _blur_vectors_call(images, counts, shapes, stream, call):
-    """The device tensors of a blur vectors call and the call itself: per image
-    (angles, magnitudes, fft_max) shaped shapes[i] + (10,), (10,), ()."""
+def _window_lists(images, windows, kw=None):
+    """The list preamble of a window call: (images, the C array of their window
+    lists, what keeps it alive, windows per image, cfg from kw -- None without)."""
+    images = _packed_images(images, cuda=True)
+    entries = _window_entries(windows, len(images))
+    cfg = None if kw is None else make_config(**{**WINDOW_DEFAULTS, **kw})
+    arr, keep = _window_array(entries)
+    return images, arr, keep, [0 if cb is None else int(cb.N) for cb in keep], cfg
+
+
+def _window_grids(images, window, stride, kw=None):
+    """The grid preamble of a window call: (images, the stride, window_grid's
+    shape per image -- (0, 0) where the library refuses the window or the stride
+    --, cfg from kw -- None without)."""
+    images = _packed_images(images, cuda=True)
+    stride = window if stride is None else int(stride)
+    cfg = None if kw is None else make_config(**{**WINDOW_DEFAULTS, **kw})
+    grids = [window_grid(int(im.shape[0]), int(im.shape[1]), window, stride)[1] if stride > 0 and window > 0
+             else (0, 0) for im in images]
+    return images, stride, grids, cfg
+
+
+def _window_call(name, images, counts, shapes, outputs, stream, call):
+    """The device tensors of a window call and the call itself.  outputs: (per
+    output array of the C entry its (dtype, trailing shape), or None for one not
+    asked for -- a NULL array; form); call(pointers, heights, widths, n, *output
+    arrays, stream handle) is the entry; form(*an image's tensors, each shaped
+    shapes[i] + its trailing shape) is the image's result."""
     import torch
     n = len(images)
-    vec = [torch.empty((c, 10, 2), dtype=torch.int32, device=im.device) for im, c in zip(images, counts)]
-    fmax = [torch.empty((c,), dtype=torch.float64, device=im.device) for im, c in zip(images, counts)]
+    if n == 0:
+        return []
+    specs, form = outputs
+    outs = [None if s is None else [torch.empty((c,) + s[1], dtype=s[0], device=im.device)
+                                    for im, c in zip(images, counts)] for s in specs]
+    live = [ts for ts in outs if ts is not None]
     if stream is not None:
-        for t in vec + fmax:
+        for t in sum(live, []):
             t.record_stream(stream)
     ptrs, hs, ws = _image_arrays(images)
-    pv = (ctypes.c_void_p * n)(*[v.data_ptr() if c else None for v, c in zip(vec, counts)])
-    pf = (ctypes.c_void_p * n)(*[f.data_ptr() if c else None for f, c in zip(fmax, counts)])
-    call(ptrs, hs, ws, n, pv, pf, _stream_handle(stream))
-    out = []
-    for v, f, shp in zip(vec, fmax, shapes):
-        v = v.reshape(tuple(shp) + (10, 2))
-        out.append((v[..., 0], v[..., 1].view(torch.float32), f.reshape(tuple(shp))))
-    return out
+    arrays = [None if ts is None else (ctypes.c_void_p * n)(*[t.data_ptr() if c else None for t, c in zip(ts, counts)])
+              for ts in outs]
+    if call(ptrs, hs, ws, n, *arrays, _stream_handle(stream)) != 0:
+        raise RuntimeError(f"{name} failed: {last_error()}")
+    return [form(*[t.reshape(tuple(shp) + tuple(t.shape[1:])) for t in ts]) for ts, shp in zip(zip(*live), shapes)]
+
+
+def _vector_outputs():
+    """_window_call's outputs of the blur vector entries: per image (angles,
+    magnitudes, fft_max) shaped shapes[i] + (10,), (10,), ()."""
+    import torch
+    return ([(torch.int32, (10, 2)), (torch.float64, ())],
+            lambda v, f: (v[..., 0], v[..., 1].view(torch.float32), f))
+
+
+def _sharpness_outputs(variance):
+    """_window_call's outputs of the window sharpness entries: per image the
+    sharpness shaped shapes[i], or (sharpness, variance)."""
+    import torch
+    spec = (torch.float64, ())
+    return [spec, spec if variance else None], (lambda s, v: (s, v)) if variance else (lambda s: s)
 
 
 def blur_vectors_device(images, windows, window=128, stream=None, **kw):
@@ -1041,20 +1083,10 @@ def blur_vectors_device(images, windows, window=128, stream=None, **kw):
     Inputs and kw as blur_windows_device; angle_partitions must be at least 2.
     Nothing is copied to the host; with stream= the call is enqueued on that
     stream and the tensors are valid in its order."""
-    images = _packed_images(images, cuda=True)
-    n = len(images)
-    entries = _window_entries(windows, n)
-    cfg = make_config(**{**WINDOW_DEFAULTS, **kw})
-    if n == 0:
-        return []
-    arr, keep = _window_array(entries)
-    counts = [0 if cb is None else int(cb.N) for cb in keep]
-
-    def call(ptrs, hs, ws, n, pv, pf, s):
-        if lib.phd_blur_vectors_device(ptrs, hs, ws, n, arr, int(window), ctypes.byref(cfg), pv, pf, s) != 0:
-            raise RuntimeError(f"blur_vectors_device failed: {last_error()}")
-
-    return _blur_vectors_call(images, counts, [(c,) for c in counts], stream, call)
+    images, arr, keep, counts, cfg = _window_lists(images, windows, kw)
+    return _window_call("blur_vectors_device", images, counts, [(c,) for c in counts], _vector_outputs(), stream,
+                        lambda ptrs, hs, ws, n, pv, pf, s: lib.phd_blur_vectors_device(
+                            ptrs, hs, ws, n, arr, int(window), ctypes.byref(cfg), pv, pf, s))
 
 
 def blur_vector_maps_device(images, window=128, stride=None, stream=None, **kw):
@@ -1063,40 +1095,10 @@ def blur_vector_maps_device(images, window=128, stride=None, stream=None, **kw):
     [gh, gw, 10] int32, magnitudes [gh, gw, 10] float32, fft_max [gh, gw]
     float64) -- blur_map_device's vectors and maxima without its bins, and
     without a copy to the host."""
-    images = _packed_images(images, cuda=True)
-    n = len(images)
-    stride = window if stride is None else int(stride)
-    cfg = make_config(**{**WINDOW_DEFAULTS, **kw})
-    if n == 0:
-        return []
-    grids = [window_grid(int(im.shape[0]), int(im.shape[1]), window, stride)[1] if stride > 0 and window > 0
-             else (0, 0) for im in images]
-
-    def call(ptrs, hs, ws, n, pv, pf, s):
-        if lib.phd_blur_vector_maps_device(ptrs, hs, ws, n, int(window), stride, ctypes.byref(cfg), pv, pf, s) != 0:
-            raise RuntimeError(f"blur_vector_maps_device failed: {last_error()}")
-
-    return _blur_vectors_call(images, [g[0] * g[1] for g in grids], grids, stream, call)
-
-
-def _sharpness_windows_call(images, counts, shapes, variance, stream, call):
-    """The device tensors of a window sharpness call and the call itself: per
-    image the sharpness shaped shapes[i], or (sharpness, variance)."""
-    import torch
-    n = len(images)
-    sharp = [torch.empty((c,), dtype=torch.float64, device=im.device) for im, c in zip(images, counts)]
-    var = [torch.empty((c,), dtype=torch.float64, device=im.device) for im, c in zip(images, counts)] if variance else []
-    if stream is not None:
-        for t in sharp + var:
-            t.record_stream(stream)
-    ptrs, hs, ws = _image_arrays(images)
-    ps = (ctypes.c_void_p * n)(*[s.data_ptr() if c else None for s, c in zip(sharp, counts)])
-    pv = (ctypes.c_void_p * n)(*[v.data_ptr() if c else None for v, c in zip(var, counts)]) if variance else None
-    call(ptrs, hs, ws, n, ps, pv, _stream_handle(stream))
-    sharp = [s.reshape(tuple(shp)) for s, shp in zip(sharp, shapes)]
-    if not variance:
-        return sharp
-    return [(s, v.reshape(tuple(shp))) for s, v, shp in zip(sharp, var, shapes)]
+    images, stride, grids, cfg = _window_grids(images, window, stride, kw)
+    return _window_call("blur_vector_maps_device", images, [g[0] * g[1] for g in grids], grids, _vector_outputs(),
+                        stream, lambda ptrs, hs, ws, n, pv, pf, s: lib.phd_blur_vector_maps_device(
+                            ptrs, hs, ws, n, int(window), stride, ctypes.byref(cfg), pv, pf, s))
 
 
 def sharpness_windows_device(images, windows, window=64, variance=False, stream=None):
@@ -1111,19 +1113,11 @@ def sharpness_windows_device(images, windows, window=64, variance=False, stream=
     throughout).  One launch takes every window of every image; nothing is copied
     to the host; with stream= the call is enqueued on that stream and the tensors
     are valid in its order."""
-    images = _packed_images(images, cuda=True)
-    n = len(images)
-    entries = _window_entries(windows, n)
-    if n == 0:
-        return []
-    arr, keep = _window_array(entries)
-    counts = [0 if cb is None else int(cb.N) for cb in keep]
-
-    def call(ptrs, hs, ws, n, ps, pv, s):
-        if lib.phd_sharpness_windows_device(ptrs, hs, ws, n, arr, int(window), ps, pv, s) != 0:
-            raise RuntimeError(f"sharpness_windows_device failed: {last_error()}")
-
-    return _sharpness_windows_call(images, counts, [(c,) for c in counts], variance, stream, call)
+    images, arr, keep, counts, _ = _window_lists(images, windows)
+    return _window_call("sharpness_windows_device", images, counts, [(c,) for c in counts],
+                        _sharpness_outputs(variance), stream,
+                        lambda ptrs, hs, ws, n, ps, pv, s: lib.phd_sharpness_windows_device(
+                            ptrs, hs, ws, n, arr, int(window), ps, pv, s))
 
 
 def sharpness_maps_device(images, window=64, stride=None, variance=False, stream=None):
@@ -1131,19 +1125,11 @@ def sharpness_maps_device(images, window=64, stride=None, variance=False, stream
     the library (phd_sharpness_maps_device): per image a float64 device tensor
     [gh, gw], or with variance=True a pair of them.  At window 64 and 128 the grid
     is blur_vector_maps_device's."""
-    images = _packed_images(images, cuda=True)
-    n = len(images)
-    stride = window if stride is None else int(stride)
-    if n == 0:
-        return []
-    grids = [window_grid(int(im.shape[0]), int(im.shape[1]), window, stride)[1] if stride > 0 and window > 0
-             else (0, 0) for im in images]
-
-    def call(ptrs, hs, ws, n, ps, pv, s):
-        if lib.phd_sharpness_maps_device(ptrs, hs, ws, n, int(window), stride, ps, pv, s) != 0:
-            raise RuntimeError(f"sharpness_maps_device failed: {last_error()}")
-
-    return _sharpness_windows_call(images, [g[0] * g[1] for g in grids], grids, variance, stream, call)
+    images, stride, grids, _ = _window_grids(images, window, stride)
+    return _window_call("sharpness_maps_device", images, [g[0] * g[1] for g in grids], grids,
+                        _sharpness_outputs(variance), stream,
+                        lambda ptrs, hs, ws, n, ps, pv, s: lib.phd_sharpness_maps_device(
+                            ptrs, hs, ws, n, int(window), stride, ps, pv, s))
 
 
 def set_bounding_boxes(bounding_boxes):

@@ -12,13 +12,16 @@
 // each window's ten vectors and its maximum in device memory, finished by the
 // window's own block; their twin phd_debug_window_vectors_host and the finish
 // alone, phd_debug_window_finish_host.
-// Plan, box rule, index maps and the finish's rows: blur_window.h; kernels:
-// blur_windows.hip.
+// The entries' windows -- checks, counts and the walk that fills recs and the
+// vectors' table -- are a WindowPlan and the twins' checks window_twin_why
+// (window_call.h); the vectors' launch goes through table_call (phd_host.h).
+// Plan of a size, box rule, index maps and the finish's rows: blur_window.h;
+// kernels: blur_windows.hip.
 
 #include <cstring>
 
 #include "phd_host.h"
-#include "blur_window.h"
+#include "window_call.h"
 
 using namespace phd;
 
@@ -57,26 +60,6 @@ bool window_grid_why(int window, const phd_config* cfg, std::string* why, const 
                false;
     *tab = host_window_table(window, cfg->radius_partitions, cfg->angle_partitions);
     if (!(*tab)->why.empty()) return *why = "window " + std::to_string(window) + ": " + (*tab)->why, false;
-    return true;
-}
-
-bool window_box_why(const Crop_Boundaries* b, int k, int T, int height, int width, std::string* why) {
-    const long long top = b->top[k], bottom = b->bottom[k], left = b->left[k], right = b->right[k];
-    const std::string box = "window " + std::to_string(k) + " (top " + std::to_string(top) + ", bottom " +
-                            std::to_string(bottom) + ", left " + std::to_string(left) + ", right " +
-                            std::to_string(right) + ")";
-    const int rule = win_box_check(b->top[k], b->bottom[k], b->left[k], b->right[k], T, height, width);
-    if (rule == 1) return *why = box + " is not " + std::to_string(T) + " x " + std::to_string(T), false;
-    if (rule == 2)
-        return *why = box + " leaves the " + std::to_string(height) + " x " + std::to_string(width) + " image", false;
-    return true;
-}
-
-bool window_list_why(const Crop_Boundaries* b, int T, int height, int width, std::string* why) {
-    if (!b || b->N == 0) return true;
-    if (b->N < 0 || !b->top || !b->bottom || !b->left || !b->right) return *why = "bad window list", false;
-    for (int k = 0; k < b->N; k++)
-        if (!window_box_why(b, k, T, height, width, why)) return false;
     return true;
 }
 
@@ -126,43 +109,32 @@ extern "C" int phd_blur_windows_device(const uint8_t* const* d_images, const int
     };
     if (out && n_images > 0)
         for (int i = 0; i < n_images; i++) out[i] = kNoWindows;
-    if (!d_images || !heights || !widths || !windows || !out || !cfg) return bad("NULL argument");
-    if (n_images <= 0) return bad("n_images must be positive");
+    WindowPlan plan(d_images, heights, widths, n_images, windows, true, window, 0);
     std::string why;
     const HostTable* ht = nullptr;
-    if (!window_grid_why(window, cfg, &why, &ht)) return bad(why);
+    if (!plan.args_why(out && cfg, &why) || !window_grid_why(window, cfg, &why, &ht) ||
+        !plan.build(nullptr, nullptr, &why))                 // (results go to `out`: no destination array)
+        return bad(why);
     const int T = window;
-    std::vector<WinRec> recs;
-    for (int i = 0; i < n_images; i++) {
-        const std::string img = "image " + std::to_string(i) + ": ";
-        if (!d_images[i]) return bad(img + "NULL image");
-        if (heights[i] < T || widths[i] < T)
-            return bad(img + std::to_string(heights[i]) + " x " + std::to_string(widths[i]) +
-                       " is smaller than the window " + std::to_string(T));
-        if (!window_list_why(windows[i], T, heights[i], widths[i], &why)) return bad(img + why);
-        const Crop_Boundaries* b = windows[i];
-        for (int k = 0; b && k < b->N; k++)
-            recs.push_back(WinRec{d_images[i] + 3LL * ((long long)b->top[k] * widths[i] + b->left[k]),
-                                  3LL * widths[i]});
-    }
     const int na = cfg->angle_partitions, nr = cfg->radius_partitions, nbins = na * nr;
-    if (recs.empty()) {                                      // no window at all: nothing for the device
+    if (plan.total == 0) {                                   // no window at all: nothing for the device
         for (int i = 0; i < n_images; i++) window_blur_alloc(&out[i], 0, ht->t);
         return 0;
     }
-    if (recs.size() > 0x7FFFFFFFu) return bad("too many windows");
     for (int i = 0; i < n_images; i++)
-        if (!window_blur_alloc(&out[i], windows[i] ? windows[i]->N : 0, ht->t)) {
+        if (!window_blur_alloc(&out[i], (int)plan.count[i], ht->t)) {
             phd_free_window_blur(out, n_images);
             return -1;
         }
-    // window w of the call -> its image's arrays
-    std::vector<std::pair<int, int>> where(recs.size());
-    {
-        size_t w = 0;
-        for (int i = 0; i < n_images; i++)
-            for (int k = 0; k < out[i].n_windows; k++) where[w++] = {i, k};
-    }
+    // window w of the call: its record, and -> its image's arrays
+    std::vector<WinRec> recs;
+    std::vector<std::pair<int, int>> where;
+    recs.reserve(plan.total);
+    where.reserve(plan.total);
+    plan.for_each([&](int i, long long k, long long top, long long left) {
+        recs.push_back(WinRec{d_images[i] + 3LL * (top * widths[i] + left), 3LL * widths[i]});
+        where.push_back({i, (int)k});
+    });
     Context* c = get_context();
     if (!c) {
         phd_free_window_blur(out, n_images);
@@ -262,94 +234,50 @@ bool vector_grid_why(int window, const phd_config* cfg, std::string* why, const 
     return true;
 }
 
-// Both vector entries: window lists (stride 0) or a regular grid per image (stride > 0).
-int blur_vectors_call(const char* entry, const uint8_t* const* d_images, const int* heights, const int* widths,
-                      int n_images, const Crop_Boundaries* const* windows, int window, int stride,
-                      const phd_config* cfg, Blur_Vector* const* d_vectors, double* const* d_fft_max, void* stream) {
+// Both vector entries: the plan of their windows (lists, or a regular grid per image).
+int blur_vectors_call(const char* entry, WindowPlan plan, const phd_config* cfg, Blur_Vector* const* d_vectors,
+                      double* const* d_fft_max, void* stream) {
     clear_error();
-    auto bad = [&](const std::string& what) {
-        set_error(std::string(entry) + ": " + what);
-        return -1;
-    };
-    const bool grid = !windows;
-    if (!d_images || !heights || !widths || !d_vectors || !cfg) return bad("NULL argument");
-    if (n_images <= 0) return bad("n_images must be positive");
     std::string why;
     const HostTable* ht = nullptr;
-    if (!vector_grid_why(window, cfg, &why, &ht)) return bad(why);
-    if (grid && stride <= 0) return bad("stride must be positive, not " + std::to_string(stride));
-    const int T = window;
-    // windows of image i: windows[i]->N, or the grid's gh * gw (window_grid's rule)
-    std::vector<long long> count(n_images, 0), gws(n_images, 0);
-    long long nw = 0;
-    for (int i = 0; i < n_images; i++) {
-        const std::string img = "image " + std::to_string(i) + ": ";
-        if (!d_images[i]) return bad(img + "NULL image");
-        if (heights[i] < T || widths[i] < T)
-            return bad(img + std::to_string(heights[i]) + " x " + std::to_string(widths[i]) +
-                       " is smaller than the window " + std::to_string(T));
-        if (grid) {
-            gws[i] = (widths[i] - T) / stride + 1;
-            count[i] = ((long long)(heights[i] - T) / stride + 1) * gws[i];
-        } else {
-            if (!window_list_why(windows[i], T, heights[i], widths[i], &why)) return bad(img + why);
-            count[i] = windows[i] ? windows[i]->N : 0;
-        }
-        if (count[i] > 0 && !d_vectors[i])
-            return bad(img + "NULL d_vectors for " + std::to_string(count[i]) + " windows");
-        nw += count[i];
+    if (!plan.args_why(d_vectors && cfg, &why) || !vector_grid_why(plan.T, cfg, &why, &ht) ||
+        !plan.build((const void* const*)d_vectors, "d_vectors", &why)) {
+        set_error(std::string(entry) + ": " + why);
+        return -1;
     }
-    if (nw == 0) return 0;                                   // no window at all: nothing for the device
-    if (nw > 0x7FFFFFFFLL) return bad("too many windows");
-    const int na = cfg->angle_partitions, nr = cfg->radius_partitions, nbins = na * nr;
+    if (plan.total == 0) return 0;                           // no window at all: nothing for the device
+    const int T = plan.T, na = cfg->angle_partitions, nr = cfg->radius_partitions, nbins = na * nr;
+    const size_t nw = (size_t)plan.total;
     Context* c = get_context();
     if (!c) return -1;
     std::lock_guard<std::mutex> lk(c->mu);
-    const hipStream_t st = work_stream(c, stream);
+    const BlurTable* tbl = get_table(c, T, T, nr, na);
+    if (!tbl) return -1;
     // the call's table: twiddles | the bins' element counts (u16) | window records | their destinations
     const size_t o_counts = al(sizeof(double2) * T), o_recs = o_counts + al(sizeof(uint16_t) * nbins);
-    const size_t o_dst = o_recs + al(sizeof(WinRec) * (size_t)nw), bytes = o_dst + sizeof(WinDst) * (size_t)nw;
-    auto run = [&]() {
-        const BlurTable* tbl = get_table(c, T, T, nr, na);
-        if (!tbl) return false;
-        // the context's launch table, filled in place
-        uint8_t* h = (uint8_t*)table_begin(c, bytes);
-        if (!h) return false;
-        uint8_t* d = (uint8_t*)c->d_views;
+    const size_t o_dst = o_recs + al(sizeof(WinRec) * nw), bytes = o_dst + sizeof(WinDst) * nw;
+    auto fill = [&](uint8_t* h) {
         memset(h, 0, o_recs);
         window_twiddles(T, (double2*)h);
         uint16_t* hc = (uint16_t*)(h + o_counts);
         for (int b = 0; b < nbins; b++) hc[b] = (uint16_t)tbl->counts[b];
         WinRec* recs = (WinRec*)(h + o_recs);
         WinDst* dst = (WinDst*)(h + o_dst);
-        memset(h + o_recs + sizeof(WinRec) * (size_t)nw, 0, o_dst - o_recs - sizeof(WinRec) * (size_t)nw);
+        memset(h + o_recs + sizeof(WinRec) * nw, 0, o_dst - o_recs - sizeof(WinRec) * nw);
         size_t w = 0;
-        for (int i = 0; i < n_images; i++) {
-            const long long pitch = 3LL * widths[i];
-            for (long long k = 0; k < count[i]; k++, w++) {
-                const long long top = grid ? (k / gws[i]) * stride : windows[i]->top[k];
-                const long long left = grid ? (k % gws[i]) * stride : windows[i]->left[k];
-                recs[w] = WinRec{d_images[i] + top * pitch + 3 * left, pitch};
-                dst[w] = WinDst{(WinVector*)d_vectors[i] + kWinVectors * k,
-                                d_fft_max && d_fft_max[i] ? d_fft_max[i] + k : nullptr};
-            }
-        }
-        if (!table_upload(c, bytes, st)) return false;
-        const int ps = c->prof.begin(kWindowVectors, st);
-        const hipError_t e = launch_window_vectors(T, (const WinRec*)(d + o_recs), (const WinDst*)(d + o_dst), (int)nw,
-                                                   (const double2*)d, tbl->d_map, (const uint16_t*)(d + o_counts), na,
-                                                   nr, cfg->blur_cutoff_ratio_denom, cfg->fft_streak_thresh,
-                                                   cfg->magnitude_thresh, st);
-        c->prof.end(ps, st);
-        PHD_HIP(e);
-        if (!table_launched(c, st)) return false;
-        if (!stream) {                                       // the library's stream: waited for
-            PHD_HIP(hipStreamSynchronize(st));
-            c->prof.collect();
-        }
-        return true;
+        plan.for_each([&](int i, long long k, long long top, long long left) {
+            const long long pitch = 3LL * plan.widths[i];
+            recs[w] = WinRec{plan.d_images[i] + top * pitch + 3 * left, pitch};
+            dst[w++] = WinDst{(WinVector*)d_vectors[i] + kWinVectors * k,
+                              d_fft_max && d_fft_max[i] ? d_fft_max[i] + k : nullptr};
+        });
     };
-    return run() ? 0 : -1;
+    auto launch = [&](const uint8_t* d, hipStream_t st) {
+        return launch_window_vectors(T, (const WinRec*)(d + o_recs), (const WinDst*)(d + o_dst), (int)nw,
+                                     (const double2*)d, tbl->d_map, (const uint16_t*)(d + o_counts), na, nr,
+                                     cfg->blur_cutoff_ratio_denom, cfg->fft_streak_thresh, cfg->magnitude_thresh, st);
+    };
+    return table_call(c, stream, bytes, fill, launch, kWindowVectors) ? 0 : -1;
 }
 
 }  // namespace
@@ -358,20 +286,17 @@ extern "C" int phd_blur_vectors_device(const uint8_t* const* d_images, const int
                                        int n_images, const Crop_Boundaries* const* windows, int window,
                                        const phd_config* cfg, Blur_Vector* const* d_vectors,
                                        double* const* d_fft_max, void* stream) {
-    if (!windows) {
-        clear_error();
-        set_error("phd_blur_vectors_device: NULL argument");
-        return -1;
-    }
-    return blur_vectors_call("phd_blur_vectors_device", d_images, heights, widths, n_images, windows, window, 0, cfg,
+    return blur_vectors_call("phd_blur_vectors_device",
+                             WindowPlan(d_images, heights, widths, n_images, windows, true, window, 0), cfg,
                              d_vectors, d_fft_max, stream);
 }
 
 extern "C" int phd_blur_vector_maps_device(const uint8_t* const* d_images, const int* heights, const int* widths,
                                            int n_images, int window, int stride, const phd_config* cfg,
                                            Blur_Vector* const* d_vectors, double* const* d_fft_max, void* stream) {
-    return blur_vectors_call("phd_blur_vector_maps_device", d_images, heights, widths, n_images, nullptr, window,
-                             stride, cfg, d_vectors, d_fft_max, stream);
+    return blur_vectors_call("phd_blur_vector_maps_device",
+                             WindowPlan(d_images, heights, widths, n_images, nullptr, false, window, stride), cfg,
+                             d_vectors, d_fft_max, stream);
 }
 
 // k_window_vectors' twin: window_bins_host, then the shared finish.
@@ -379,18 +304,11 @@ extern "C" int phd_debug_window_vectors_host(const uint8_t* rgb, int height, int
                                              const Crop_Boundaries* windows, int window, const phd_config* cfg,
                                              Blur_Vector* vectors, double* fft_max) {
     clear_error();
-    std::string why;
+    std::string why, grid_why;
     const HostTable* ht = nullptr;
-    if (!rgb) why = "NULL image";
-    else if (vector_grid_why(window, cfg, &why, &ht)) {
-        if (height < window || width < window)
-            why = std::to_string(height) + " x " + std::to_string(width) + " is smaller than the window " +
-                  std::to_string(window);
-        else if (window_list_why(windows, window, height, width, &why) && windows && windows->N > 0 &&
-                 (!vectors || !fft_max))
-            why = "NULL vectors or fft_max";
-    }
-    if (!why.empty()) {
+    vector_grid_why(window, cfg, &grid_why, &ht);
+    if (!window_twin_why(rgb, height, width, windows, window, grid_why, vectors && fft_max, "NULL vectors or fft_max",
+                         &why)) {
         set_error("phd_debug_window_vectors_host: " + why);
         return -1;
     }
@@ -427,18 +345,11 @@ extern "C" int phd_debug_window_blur_host(const uint8_t* rgb, int height, int wi
                                           int window, const phd_config* cfg, double* bins, Blur_Vector* vectors,
                                           double* fft_max) {
     clear_error();
-    std::string why;
+    std::string why, grid_why;
     const HostTable* ht = nullptr;
-    if (!rgb) why = "NULL image";
-    else if (window_grid_why(window, cfg, &why, &ht)) {
-        if (height < window || width < window)
-            why = std::to_string(height) + " x " + std::to_string(width) + " is smaller than the window " +
-                  std::to_string(window);
-        else if (window_list_why(windows, window, height, width, &why) && windows && windows->N > 0 &&
-                 (!bins || !vectors || !fft_max))
-            why = "NULL bins, vectors or fft_max";
-    }
-    if (!why.empty()) {
+    window_grid_why(window, cfg, &grid_why, &ht);
+    if (!window_twin_why(rgb, height, width, windows, window, grid_why, bins && vectors && fft_max,
+                         "NULL bins, vectors or fft_max", &why)) {
         set_error("phd_debug_window_blur_host: " + why);
         return -1;
     }

@@ -505,6 +505,28 @@ void* table_begin(Context* c, size_t bytes);
 bool table_upload(Context* c, size_t bytes, hipStream_t st);
 bool upload_table(Context* c, const void* host, size_t filled, size_t bytes, hipStream_t st);
 bool table_launched(Context* c, hipStream_t st);
+// A whole call of one launch over a table of `bytes` (the window entries), under
+// the context's lock: fill(pinned block), the copy, launch(device block, st) ->
+// hipError_t under profile slot `slot`, on the caller's stream or -- stream ==
+// nullptr -- the library's, which is then waited for.
+template <class Fill, class Launch>
+bool table_call(Context* c, void* stream, size_t bytes, Fill fill, Launch launch, int slot) {
+    const hipStream_t st = work_stream(c, stream);
+    uint8_t* h = (uint8_t*)table_begin(c, bytes);
+    if (!h) return false;
+    fill(h);
+    if (!table_upload(c, bytes, st)) return false;
+    const int ps = c->prof.begin(slot, st);
+    const hipError_t e = launch((const uint8_t*)c->d_views, st);
+    c->prof.end(ps, st);
+    PHD_HIP(e);
+    if (!table_launched(c, st)) return false;
+    if (!stream) {                                           // the library's stream: waited for
+        PHD_HIP(hipStreamSynchronize(st));
+        c->prof.collect();
+    }
+    return true;
+}
 // The batched sharpness stage of n same-size device images on st: uploads the
 // box table (one copy) and enqueues the two launches.  Box sums go to out0 +
 // img * out_stride + 2 * slot (doubles); out0 == nullptr: to a flat array in

@@ -145,6 +145,26 @@ def test_grid_entry_rejects_bad_arguments_before_touching_hip():
     assert "image 0: 100 x 200 is smaller than the window 128" in call(window=128)
     msg = call(vec=(None, 2 << 20))
     assert "image 0: NULL d_vectors for 3 windows" in msg, msg          # 100 x 200 at 64 / 64: 1 x 3
+    # more than 2^31 - 1 windows: 46341^2 windows of 64 x 64 at stride 1
+    big = 46340 + 64
+    msg = call(imgs=(4096,), hs=(big,), ws=(big,), stride=1, vec=(1 << 20,))
+    assert "too many windows" in msg, msg
+    # three grids of (2^31 - 64)^2 windows: their sum does not fit a long long; refused at the first
+    top = 2147483647
+    msg = call(imgs=(4096, 8192, 12288), hs=(top,) * 3, ws=(top,) * 3, stride=1, vec=(1 << 20, 2 << 20, 3 << 20))
+    assert "too many windows" in msg, msg
+    # the running count is checked image by image: image 1's own defect is never reached
+    msg = call(imgs=(4096, None), hs=(big, 100), ws=(big, 200), stride=1)
+    assert "too many windows" in msg and "image 1" not in msg, msg
+
+
+def test_python_wrappers_without_images_return_nothing():
+    """No image: [] before any tensor or device is touched."""
+    import photohive_dsp_amd as phd
+    assert phd.blur_vectors_device([], []) == [] and phd.blur_vectors_device([], None) == []
+    assert phd.blur_vector_maps_device([]) == [] and phd.blur_vector_maps_device([], stride=0) == []
+    with pytest.raises(ValueError, match="windows has 1 entries for 0 images"):
+        phd.blur_vectors_device([], [None])
 
 
 def test_twin_and_finish_reject_bad_arguments():

@@ -369,6 +369,43 @@ def test_two_calls_back_to_back_on_a_callers_stream():
     _guards_intact(ups)
 
 
+def test_two_grid_calls_back_to_back_on_a_callers_stream():
+    """The grid entry twice through the shared table call with no synchronisation between: 70 x 133
+    (3 x 24 windows at 64 / 3) and 64 x 64 (its single window), then other images in the other order.
+    Vectors: the host twin's exactly; fft_max: the bits of the same call on the library's stream."""
+    phd, L, torch = _phd()
+    from photohive_dsp_amd import synth
+    shapes, T, stride = [(70, 133), (64, 64)], 64, 3
+    imgs = [[np.ascontiguousarray(synth.make(kind, h, w, seed)) for (h, w), seed in zip(shapes, seeds)]
+            for kind, seeds in (("motion", (96, 97)), ("dominant", (98, 99)))]
+    imgs[1].reverse()
+    ups = [[_upload(torch, im, 1 + i) for i, im in enumerate(call)] for call in imgs]
+    grids = [[phd.window_grid(*im.shape[:2], T, stride) for im in call] for call in imgs]
+    assert [g[1] for g in grids[0]] == [(3, 24), (1, 1)]
+    want = [_maps([u[1] for u in up], [im.shape[:2] for im in call], T, stride, [g[1] for g in gs])
+            for call, up, gs in zip(imgs, ups, grids)]
+    outs = [_Out(torch, [len(g[0]) for g in gs]) for gs in grids]
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())                  # the images and the guard fills are done first
+    for call, up, out in zip(imgs, ups, outs):
+        pv, pf = out.pointers()
+        rc = L.lib.phd_blur_vector_maps_device((ctypes.c_void_p * 2)(*[u[1] for u in up]),
+                                               (ctypes.c_int * 2)(*[im.shape[0] for im in call]),
+                                               (ctypes.c_int * 2)(*[im.shape[1] for im in call]), 2, T, stride,
+                                               ctypes.byref(_cfg()), pv, pf, s.cuda_stream)
+        assert rc == 0, L.last_error()
+    s.synchronize()
+    for c, (call, out) in enumerate(zip(imgs, outs)):
+        for i, (im, got) in enumerate(zip(call, out.results())):
+            twin = _twin(im, grids[c][i][0], T)
+            np.testing.assert_array_equal(got[0], twin[0], err_msg=f"call {c} image {i}: twin angles")
+            np.testing.assert_array_equal(got[1].view(np.uint32), twin[1].view(np.uint32),
+                                          err_msg=f"call {c} image {i}: twin magnitudes")
+            for a, b in zip(_bits(got), _bits(want[c][i])):
+                np.testing.assert_array_equal(a, b, err_msg=f"call {c} image {i}")
+    _guards_intact(ups[0] + ups[1])
+
+
 def test_python_wrappers():
     phd, L, torch = _phd()
     from photohive_dsp_amd import synth

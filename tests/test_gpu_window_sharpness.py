@@ -252,6 +252,34 @@ def test_two_calls_back_to_back_on_a_callers_stream():
     _guards_intact(ups)
 
 
+def test_two_grid_calls_back_to_back_on_a_callers_stream():
+    """The grid entry twice through the shared table call with no synchronisation between: 70 x 133
+    (3 x 24 windows at 64 / 3) and 64 x 64 (its single window), then other images in the other order."""
+    phd, L, torch = _phd()
+    shapes, T, stride = [(70, 133), (64, 64)], 64, 3
+    imgs = [[wsc.kind_image(kind, h, w, seed) for (h, w), seed in zip(shapes, seeds)]
+            for kind, seeds in (("uniform", (96, 97)), ("structured", (98, 99)))]
+    imgs[1].reverse()
+    ups = [[_upload(torch, im, 1 + i) for i, im in enumerate(call)] for call in imgs]
+    grids = [[phd.window_grid(*im.shape[:2], T, stride) for im in call] for call in imgs]
+    assert [g[1] for g in grids[0]] == [(3, 24), (1, 1)]
+    outs = [_Out(torch, [len(g[0]) for g in call], range(2)) for call in grids]
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())                  # the images and the guard fills are done first
+    for call, up, out in zip(imgs, ups, outs):
+        ps, pv = out.pointers()
+        rc = L.lib.phd_sharpness_maps_device((ctypes.c_void_p * 2)(*[u[1] for u in up]),
+                                             (ctypes.c_int * 2)(*[im.shape[0] for im in call]),
+                                             (ctypes.c_int * 2)(*[im.shape[1] for im in call]), 2, T, stride, ps, pv,
+                                             s.cuda_stream)
+        assert rc == 0, L.last_error()
+    s.synchronize()
+    for c, (call, out) in enumerate(zip(imgs, outs)):
+        for i, (im, got) in enumerate(zip(call, out.results())):
+            _check(im, grids[c][i][0], T, got, f"call {c} image {i}", oracle=False)
+    _guards_intact(ups[0] + ups[1])
+
+
 @pytest.mark.parametrize("T", wsc.SIZES)
 def test_special_windows(T):
     phd, L, torch = _phd()

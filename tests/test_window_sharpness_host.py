@@ -3,7 +3,8 @@
 oracle.sharpness at both bars of tests/sharp_boxes.py, and bit for bit against a
 Python big-integer restatement of the header's definition; the special windows;
 every refusal of the two device entries, which come before any HIP call; the ABI;
-and the twin under ASan + UBSan as a stand-alone program."""
+and the twin, and the plan of a window call (window_call.h), under ASan + UBSan as
+stand-alone programs."""
 import ctypes
 import math
 import os
@@ -209,6 +210,23 @@ def test_grid_entry_rejects_bad_arguments_before_touching_hip():
     big = 46340 + 16
     msg = call(imgs=(4096,), hs=(big,), ws=(big,), window=16, stride=1, sharp=(1 << 20,))
     assert "too many windows" in msg, msg
+    # three grids of (2^31 - 16)^2 windows: their sum does not fit a long long; refused at the first
+    top = 2147483647
+    msg = call(imgs=(4096, 8192, 12288), hs=(top,) * 3, ws=(top,) * 3, window=16, stride=1,
+               sharp=(1 << 20, 2 << 20, 3 << 20))
+    assert "too many windows" in msg, msg
+    # the running count is checked image by image: image 1's own defect is never reached
+    msg = call(imgs=(4096, None), hs=(big, 100), ws=(big, 200), window=16, stride=1)
+    assert "too many windows" in msg and "image 1" not in msg, msg
+
+
+def test_python_wrappers_without_images_return_nothing():
+    """No image: [] before any tensor or device is touched."""
+    import photohive_dsp_amd as phd
+    assert phd.sharpness_windows_device([], []) == [] and phd.sharpness_windows_device([], None, variance=True) == []
+    assert phd.sharpness_maps_device([]) == [] and phd.sharpness_maps_device([], stride=0, variance=True) == []
+    with pytest.raises(ValueError, match="windows has 1 entries for 0 images"):
+        phd.sharpness_windows_device([], [None])
 
 
 def test_a_call_without_windows_does_nothing_and_succeeds():
@@ -250,4 +268,23 @@ def test_host_twin_under_asan(tmp_path):
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120, env=env)
     assert r.returncode == 0, r.stdout + r.stderr[-4000:]
     assert "window sharpness host OK" in r.stdout
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
+
+
+def test_window_call_plan_under_asan(tmp_path):
+    """window_call.h alone and a C++ driver built with ASan + UBSan, run as their own
+    process: the walk against window_grid's boxes for lists and grids, every refusal
+    of the plan word for word, the counts at and far past 2^31 - 1 with no overflow
+    report, and the twins' ladder."""
+    if not shutil.which("g++"):
+        pytest.skip("no g++")
+    exe = tmp_path / "window_call_asan"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=all", "-o", str(exe),
+                    os.path.join(ROOT, "tests", "native", "window_call_asan.cpp")], check=True, timeout=300)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    env.pop("LD_PRELOAD", None)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode == 0, r.stdout + r.stderr[-4000:]
+    assert "window call OK" in r.stdout
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
