@@ -891,6 +891,66 @@ int phd_sharpness_maps_device(const uint8_t* const* d_images, const int* heights
 int phd_debug_window_sharpness_host(const uint8_t* rgb, int height, int width, const Crop_Boundaries* windows,
                                     int window, double* sharpness, double* variance, unsigned long long* sums);
 
+/* ---- statistics maps: brightness, contrast, saturation of window grids, on the device
+ * The window statistics of a T x T window (rows top <= y < top+T, columns
+ * left <= x < left+T of a packed RGB8 image: crop_image's crop,
+ * src/image_processing.c:244-266) are get_rgb_statistics
+ * (src/image_processing.c:543-553, with get_average and get_variance,
+ * src/filtering.c:125-148) and get_hsv_average over rgb2hsv's s
+ * (src/image_processing.c:533-540, 372-417) of its n = T^2 pixels: the box
+ * statistics' definition (phd_box_stats_device) restricted to square windows and
+ * finished on the device.
+ *  - M[0..2] = sum k and M[3..5] = sum k^2 per channel; n1 = #(min == 0 < max);
+ *    D[m], m = 0..255: the sum of max - min over the pixels whose max is m.  All
+ *    integers; at T = 128 each fits 32 bits and n M[3+c] - M[c]^2 fits 64.
+ *  - The finish is the only floating point, shared by the kernel and the host twin
+ *    (stat_window.h), plain IEEE fp64 operations with no fused multiply-add:
+ *      B_c   = (double)M[c] / 255.0 / (double)n
+ *      C_c   = sqrt((double)(n M[3+c] - M[c]^2) / 65025.0 / ((double)n * (double)n))
+ *      S     = sum over m = 1..255 of (double)D[m] / (double)m, ascending, sequential
+ *              (a zero term may be left out: every term is >= 0)
+ *      S-bar = (S - (1.0 - 0.999999) * (double)n1) / (double)n
+ * A window's seven values depend on its 3 T^2 bytes only: the same on every run
+ * and wherever the window sits in a call.  None is NaN or infinite.
+ *
+ * window is 16, 32, 64 or 128.  d_stats[i]: device pointer, 8-byte aligned,
+ * receives 7 * n_i doubles, window-major: Br Bg Bb Cr Cg Cb S-bar per window (n_i
+ * is windows[i]->N or gh * gw); it may be NULL only when n_i == 0.  Nothing else
+ * is written.  Images are packed RGB8 device images of any sizes from T x T at any
+ * base alignment; no byte outside a window's own pixels is read (a 4-pixel unit's
+ * 12 bytes are read at their own address).
+ * Refused with -1 before any device work (also on a machine without a GPU),
+ * phd_last_error naming image and window: NULL arguments, a NULL image,
+ * n_images <= 0, a size below T, a window size outside the four, a box whose sides
+ * are not T or that leaves the image, a non-positive stride, a NULL d_stats entry
+ * of an image that has windows, more than 2^31 - 1 windows.
+ * One launch (profile slot 17) takes every window of every image: 256-thread
+ * blocks, one window per block at 128 and 64 and one per wave at 32 and 16; the
+ * moments in registers, D in LDS, the finish in the block that summed the window;
+ * no global atomic, no zeroed buffer, no second launch.  Per call one table upload
+ * (a 16-byte record and an 8-byte destination per window) and no allocation.
+ * Enqueued on `stream` and not waited for, or (NULL) on the library's stream and
+ * waited for, as phd_pack_views_device.  A call with no window at all does no
+ * device work and returns 0.  0 or -1. */
+/* Window lists, as phd_sharpness_windows_device takes them. */
+int phd_stats_windows_device(const uint8_t* const* d_images, const int* heights, const int* widths, int n_images,
+                             const Crop_Boundaries* const* windows, int window, double* const* d_stats,
+                             void* stream);
+/* A regular grid per image: window_grid's rule, gh = (H - T) / stride + 1, gw = (W - T) / stride + 1,
+ * row-major; stride > 0, may be smaller (overlap) or larger than the window. */
+int phd_stats_maps_device(const uint8_t* const* d_images, const int* heights, const int* widths, int n_images,
+                          int window, int stride, double* const* d_stats, void* stream);
+/* Validation hook, host only (no GPU): the window statistics kernel's twin
+ * (get_rgb_statistics, src/image_processing.c:543-553, and get_hsv_average,
+ * :533-540, over rgb2hsv, :372-417, on the crops of :244-266; get_average and
+ * get_variance, src/filtering.c:125-148): the 4-pixel unit's plain form and the
+ * same finish (stat_window.h) over one packed RGB8 image of host memory at any
+ * alignment.  stats: 7 doubles per window; sums: NULL, or 264 u64 per window in
+ * the box statistics' record layout (M[6], n1, N, D[256]).  0, or -1 with
+ * phd_last_error. */
+int phd_debug_window_stats_host(const uint8_t* rgb, int height, int width, const Crop_Boundaries* windows,
+                                int window, double* stats, unsigned long long* sums);
+
 /* Palette intermediates of one device-resident image, for bit-exact checks:
  * hist[TL] (arm_octree quantities), parents[*n_parents] (valid_parents in
  * palette order), kept[*n_parents] (pixels surviving group_irregular_pixels).
@@ -1002,7 +1062,8 @@ int phd_last_timings(double* ms, int n);
  * 1 fft_rows, 2 fft_cols, 3 palette_cutoffs, 4 palette_sums, 5 sharpness,
  * 6 pack_views, 7 classify_views, 8 decode_views, 9 yuv_views,
  * 10 palette_labels, 11 box_palettes, 12 box_stats, 13 the fp64 route's
- * planar_box_stats, 14 window_blur, 15 window_vectors, 16 window_sharp).
+ * planar_box_stats, 14 window_blur, 15 window_vectors, 16 window_sharp,
+ * 17 window_stats).
  * phd_profile_kernels resets the counters; phd_profile_read returns the
  * accumulated milliseconds and launch count of one kernel. */
 int phd_profile_kernels(unsigned mask);

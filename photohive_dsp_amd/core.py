@@ -1132,6 +1132,38 @@ def sharpness_maps_device(images, window=64, stride=None, variance=False, stream
                             ptrs, hs, ws, n, int(window), stride, ps, pv, s))
 
 
+def _stats_outputs():
+    """_window_call's output of the window statistics entries: per image one tensor
+    shaped shapes[i] + (7,)."""
+    import torch
+    return [(torch.float64, (7,))], lambda s: s
+
+
+def stats_windows_device(images, windows, window=64, stream=None):
+    """Brightness, contrast and average saturation of every window, left on the
+    device (phd_stats_windows_device): per image a float64 device tensor [n, 7] --
+    Br Bg Bb Cr Cg Cb S-bar, the reference's get_rgb_statistics and
+    get_hsv_average on each window's crop.  images and windows as
+    sharpness_windows_device takes them (`window` is 16, 32, 64 or 128).  One
+    launch takes every window of every image; nothing is copied to the host; with
+    stream= the call is enqueued on that stream and the tensors are valid in its
+    order."""
+    images, arr, keep, counts, _ = _window_lists(images, windows)
+    return _window_call("stats_windows_device", images, counts, [(c,) for c in counts], _stats_outputs(), stream,
+                        lambda ptrs, hs, ws, n, ps, s: lib.phd_stats_windows_device(
+                            ptrs, hs, ws, n, arr, int(window), ps, s))
+
+
+def stats_maps_device(images, window=64, stride=None, stream=None):
+    """stats_windows_device over window_grid of every image, the grid formed by the
+    library (phd_stats_maps_device): per image a float64 device tensor
+    [gh, gw, 7].  The grid is sharpness_maps_device's."""
+    images, stride, grids, _ = _window_grids(images, window, stride)
+    return _window_call("stats_maps_device", images, [g[0] * g[1] for g in grids], grids, _stats_outputs(), stream,
+                        lambda ptrs, hs, ws, n, ps, s: lib.phd_stats_maps_device(
+                            ptrs, hs, ws, n, int(window), stride, ps, s))
+
+
 def set_bounding_boxes(bounding_boxes):
     """core.py:489-515."""
     n = len(bounding_boxes)

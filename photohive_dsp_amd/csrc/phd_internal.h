@@ -343,6 +343,14 @@ struct SharpWinRec;
 struct SharpWinDst;
 hipError_t launch_window_sharp(int T, const SharpWinRec* d_recs, const SharpWinDst* d_dst, int n, hipStream_t st);
 
+// ---- window statistics (window_stats.hip; finish and table: stat_window.h) ----------
+// Per T x T window (T = 16, 32, 64 or 128) of a packed RGB8 image its brightness,
+// contrast and average saturation, seven doubles at d_dst[w] (8-byte aligned): n
+// windows, one launch.
+constexpr int kProfWindowStats = 17;
+struct StatWinRec;
+hipError_t launch_window_stats(int T, const StatWinRec* d_recs, double* const* d_dst, int n, hipStream_t st);
+
 // Row pass: luma - avg of two rows as one complex sequence, FFT, split, write
 // the half spectra column-major into inter[wf][height].
 // Runtime-plan FFT passes over a batch of same-size images in one launch each
