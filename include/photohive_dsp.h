@@ -1102,6 +1102,11 @@ int phd_install_crash_maps(const char* prefix);
  * pool threads); start != 0 creates them first. */
 int phd_debug_library_threads(int start);
 
+/* Test hook: the bytes of the grow-only device and pinned blocks of the current
+ * device's contexts (lanes summed; plans and tables not counted).  Creates no
+ * context: 0, 0 before the first call and after phd_shutdown.  Returns 0. */
+int phd_debug_context_bytes(unsigned long long* device, unsigned long long* pinned);
+
 #ifdef __cplusplus
 }
 #endif

@@ -151,14 +151,14 @@ extern "C" int phd_blur_windows_device(const uint8_t* const* d_images, const int
     auto run = [&]() {
         const BlurTable* tbl = get_table(c, T, T, nr, na);
         if (!tbl) return false;
-        if (!ensure_device(&c->d_winblur, &c->winblur_bytes, total)) return false;
-        if (!grow_pinned(&c->h_winblur, &c->h_winblur_bytes, std::max(up, down))) return false;
-        uint8_t* h = (uint8_t*)c->h_winblur;
-        uint8_t* d = (uint8_t*)c->d_winblur;
+        Staged& S = c->staged[kStWinBlur];
+        if (!S.reserve(total, std::max(up, down))) return false;
+        uint8_t* h = S.h.as<uint8_t>();
+        uint8_t* d = S.d.as<uint8_t>();
         memset(h, 0, o_recs);
         window_twiddles(T, (double2*)h);
         memcpy(h + o_recs, recs.data(), sizeof(WinRec) * nw);
-        PHD_HIP(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, st));
+        if (!S.up(up, st)) return false;
         HostPool* pool = host_pool();
         for (size_t w0 = 0; w0 < nw; w0 += chunk) {
             const int m = (int)std::min(chunk, nw - w0);
@@ -166,8 +166,7 @@ extern "C" int phd_blur_windows_device(const uint8_t* const* d_images, const int
             PHD_HIP(launch_window_blur(T, (const WinRec*)(d + o_recs) + w0, m, (const double2*)d, tbl->d_map, nbins,
                                        (unsigned long long*)(d + o_bins), (double*)(d + o_fmax), st));
             c->prof.end(ps, st);
-            // (stream order: the table has gone up before this copy overwrites the pinned block)
-            PHD_HIP(hipMemcpyAsync(h, d + o_bins, down, hipMemcpyDeviceToHost, st));
+            if (!S.down(o_bins, down, st)) return false;
             PHD_HIP(hipStreamSynchronize(st));               // the result is on the host: waited for on any stream
             const unsigned long long* hb = (const unsigned long long*)h;
             const double* hf = (const double*)(h + (o_fmax - o_bins));

@@ -81,14 +81,14 @@ bool box_palette_fill(phd_box_palette* bp, int n_boxes, int n_slots, const uint3
 }
 
 // The job's launch on st: records | items go up as one table, the counters
-// (Context::d_boxpal) are zeroed by one memset and come down into h_boxpal by
+// (kStBoxPal) are zeroed by one memset and come down into its pinned block by
 // one copy.  The items are walked by persistent blocks, so no table needs a
 // second launch.  The caller waits for st.
 bool enqueue_box_job(Context* c, const BoxJob& job, hipStream_t st) {
     const size_t cbytes = sizeof(unsigned) * (size_t)job.counters;
-    if (!ensure_device(&c->d_boxpal, &c->boxpal_bytes, cbytes)) return false;
-    if (!grow_pinned(&c->h_boxpal, &c->h_boxpal_bytes, cbytes)) return false;
-    PHD_HIP(hipMemsetAsync(c->d_boxpal, 0, cbytes, st));
+    Staged& S = c->staged[kStBoxPal];
+    if (!S.reserve(cbytes, cbytes)) return false;
+    PHD_HIP(hipMemsetAsync(S.d.as(), 0, cbytes, st));
     if (!job.items.empty()) {
         if (job.items.size() > 0x7FFFFFFFu) {
             set_error("box palettes: too many items");
@@ -104,13 +104,13 @@ bool enqueue_box_job(Context* c, const BoxJob& job, hipStream_t st) {
         memcpy(tab + o_items, job.items.data(), sizeof(BoxItem) * job.items.size());
         if (!table_upload(c, bytes, st)) return false;
         const int ps = c->prof.begin(kBoxPalettes, st);
-        PHD_HIP(launch_box_counts((const BoxRec*)c->d_views, (const BoxItem*)((const uint8_t*)c->d_views + o_items),
-                                  (int)job.items.size(), (unsigned*)c->d_boxpal, st));
+        const uint8_t* dt = c->staged[kStViews].d.as<const uint8_t>();
+        PHD_HIP(launch_box_counts((const BoxRec*)dt, (const BoxItem*)(dt + o_items), (int)job.items.size(),
+                                  S.d.as<unsigned>(), st));
         c->prof.end(ps, st);
         if (!table_launched(c, st)) return false;
     }
-    PHD_HIP(hipMemcpyAsync(c->h_boxpal, c->d_boxpal, cbytes, hipMemcpyDeviceToHost, st));
-    return true;
+    return S.down(0, cbytes, st);
 }
 
 }  // namespace phd
@@ -160,7 +160,7 @@ extern "C" int phd_box_palettes_device(const uint16_t* const* d_labels, const in
         return true;
     };
     if (!run()) return -1;
-    const unsigned* h = (const unsigned*)c->h_boxpal;
+    const unsigned* h = c->staged[kStBoxPal].h.as<const unsigned>();
     for (int i = 0; i < n_maps; i++) {
         if (!box_palette_fill(&out[i], nb[i], n_slots[i], h)) {
             phd_free_box_palettes(out, n_maps);

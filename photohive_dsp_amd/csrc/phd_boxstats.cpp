@@ -76,11 +76,12 @@ bool box_stats_fill(phd_box_stats* bs, const Crop_Boundaries* b, const unsigned 
     return true;
 }
 
-const unsigned long long* box_stats_host(const Context* c) { return (const unsigned long long*)c->h_boxstat; }
+const unsigned long long* box_stats_host(const Context* c) {
+    return c->staged[kStBoxStat].h.as<const unsigned long long>();
+}
 
 // Own buffers, not the launch tables' (upload_table): a report run enqueues the
 // job on its FFT stream while its tail stream's label launches use that table.
-// Every call drains its streams before it returns, so no copy reads an old block.
 bool enqueue_box_stat_job(Context* c, const BoxStatJob& job, hipStream_t st) {
     if (job.recs.empty()) return true;
     if (job.items.size() > 0x7FFFFFFFu) {
@@ -89,14 +90,14 @@ bool enqueue_box_stat_job(Context* c, const BoxStatJob& job, hipStream_t st) {
     }
     const BoxStatLayout L(job);
     const size_t nb = job.recs.size(), fin_bytes = sizeof(unsigned long long) * kBoxStatOut * nb;
-    if (!ensure_device(&c->d_boxstat, &c->boxstat_bytes, L.total)) return false;
-    if (!grow_pinned(&c->h_boxstat, &c->h_boxstat_bytes, std::max(L.up, fin_bytes))) return false;
-    uint8_t* h = (uint8_t*)c->h_boxstat;
-    uint8_t* d = (uint8_t*)c->d_boxstat;
+    Staged& S = c->staged[kStBoxStat];
+    if (!S.reserve(L.total, std::max(L.up, fin_bytes))) return false;
+    uint8_t* h = S.h.as<uint8_t>();
+    uint8_t* d = S.d.as<uint8_t>();
     memset(h, 0, L.up);
     memcpy(h, job.recs.data(), sizeof(BoxStatRec) * nb);
     memcpy(h + L.o_items, job.items.data(), sizeof(BoxItem) * job.items.size());
-    PHD_HIP(hipMemcpyAsync(d, h, L.up, hipMemcpyHostToDevice, st));
+    if (!S.up(L.up, st)) return false;
     PHD_HIP(hipMemsetAsync(d + L.o_sums, 0, sizeof(unsigned long long) * kBoxStatRec * nb, st));
     const int ps = c->prof.begin(kBoxStats, st);
     PHD_HIP(launch_box_stats((const BoxStatRec*)d, (const BoxItem*)(d + L.o_items), (int)job.items.size(),
@@ -104,9 +105,7 @@ bool enqueue_box_stat_job(Context* c, const BoxStatJob& job, hipStream_t st) {
     c->prof.end(ps, st);
     PHD_HIP(launch_box_stats_finish((const unsigned long long*)(d + L.o_sums), (int)nb,
                                     (unsigned long long*)(d + L.o_fin), st));
-    // (the table has been read by the time this copy overwrites it: stream order)
-    PHD_HIP(hipMemcpyAsync(h, d + L.o_fin, fin_bytes, hipMemcpyDeviceToHost, st));
-    return true;
+    return S.down(L.o_fin, fin_bytes, st);
 }
 
 }  // namespace phd

@@ -220,45 +220,6 @@ hipStream_t work_stream(Context* c, void* stream) {
     return c->stream;
 }
 
-// A growth frees the old buffer only once the device is idle (round 6, ADVICE
-// r5: a pinned or device block freed under an in-flight copy would be a
-// use-after-unmap; every entry point drains its streams before it returns,
-// so this is belt and braces, and growth is rare).
-bool ensure_device(void** p, size_t* cap, size_t need) {
-    if (*cap >= need && *p) return true;
-    if (*p) {
-        (void)hipDeviceSynchronize();
-        (void)hipFree(*p);
-    }
-    *p = nullptr;
-    *cap = 0;
-    size_t sz = need + need / 4 + 4096;
-    if (hipMalloc(p, sz) != hipSuccess) {
-        set_error("hipMalloc of " + std::to_string(sz) + " bytes failed");
-        *p = nullptr;
-        return false;
-    }
-    *cap = sz;
-    return true;
-}
-
-bool ensure_pinned(Context* c, size_t need) {
-    if (c->pin_bytes >= need && c->h_pin) return true;
-    if (c->h_pin) {
-        (void)hipDeviceSynchronize();
-        (void)hipHostFree(c->h_pin);
-    }
-    c->h_pin = nullptr;
-    size_t sz = need + need / 4 + 4096;
-    if (hipHostMalloc(&c->h_pin, sz, hipHostMallocDefault) != hipSuccess) {
-        set_error("hipHostMalloc failed");
-        c->pin_bytes = 0;
-        return false;
-    }
-    c->pin_bytes = sz;
-    return true;
-}
-
 // ---- FFT plans ---------------------------------------------------------------
 bool make_fft_plan(int n, FftPlanHost* p, bool composite) {
     if (n < 1 || n > kFftMaxLds) {
@@ -562,39 +523,11 @@ void destroy_context(Context* c) {
         dfree(kv.second.d_bhat);
     }
     for (auto& kv : c->cls) dfree(kv.second.d);
-    dfree(c->d_gbuf);
-    dfree(c->d_planes);
-    dfree(c->d_prec);
-    dfree(c->d_ws);
-    dfree(c->d_inter);
-    dfree(c->d_stage);
-    dfree(c->d_ptrs);
-    dfree(c->d_sharp);
-    if (c->h_sharp) (void)hipHostFree(c->h_sharp);
-    c->h_sharp = nullptr;
-    dfree(c->d_vstage);
-    dfree(c->d_views);
+    for (DevBuf& b : c->dev) b.release();
+    for (Staged& s : c->staged) s.release();
+    c->pin.release();
     dfree(c->d_snap);
-    if (c->h_views) (void)hipHostFree(c->h_views);
-    c->h_views = nullptr;
     ev_destroy(c->ev_views);
-    dfree(c->d_boxpal);
-    dfree(c->d_labscratch);
-    if (c->h_boxpal) (void)hipHostFree(c->h_boxpal);
-    c->h_boxpal = nullptr;
-    dfree(c->d_boxstat);
-    c->boxstat_bytes = 0;
-    if (c->h_boxstat) (void)hipHostFree(c->h_boxstat);
-    c->h_boxstat = nullptr;
-    c->h_boxstat_bytes = 0;
-    dfree(c->d_winblur);
-    c->winblur_bytes = 0;
-    if (c->h_winblur) (void)hipHostFree(c->h_winblur);
-    c->h_winblur = nullptr;
-    c->h_winblur_bytes = 0;
-    for (auto& p : c->d_stage2) dfree(p);
-    if (c->h_pin) (void)hipHostFree(c->h_pin);
-    c->h_pin = nullptr;
     if (c->h2d_slots) (void)hipHostFree(c->h2d_slots);
     c->h2d_slots = nullptr;
     for (auto& e : c->ev) ev_destroy(e);
@@ -766,6 +699,22 @@ extern "C" int phd_debug_library_threads(int start) {
         (void)phd::copy_pool();
     }
     return phd::library_threads();
+}
+
+extern "C" int phd_debug_context_bytes(unsigned long long* device, unsigned long long* pinned) {
+    unsigned long long d = 0, h = 0;
+    for (phd::Context* c : phd::device_contexts()) {     // summed over the lanes
+        std::lock_guard<std::mutex> lk(c->mu);
+        for (const phd::DevBuf& b : c->dev) d += b.capacity();
+        for (const phd::Staged& s : c->staged) {
+            d += s.d.capacity();
+            h += s.h.capacity();
+        }
+        h += c->pin.capacity();
+    }
+    if (device) *device = d;
+    if (pinned) *pinned = h;
+    return 0;
 }
 
 extern "C" int phd_set_lanes(int lanes) {

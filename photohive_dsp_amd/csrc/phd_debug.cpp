@@ -196,7 +196,8 @@ extern "C" int phd_debug_time_kernel(int kernel, const uint8_t* d_rgb, int heigh
     if (!cls || !tbl || !select_fft(c, height, width, cfg->radius_partitions * cfg->angle_partitions, &d_rgb, 1, &fs, tbl))
         return -1;
     // scratch outputs in the (large enough) workspace of the report just run
-    uint8_t* dw = (uint8_t*)c->d_ws;
+    uint8_t* dw = c->dev[kDevWs].as<uint8_t>();
+    double2* const inter = c->dev[kDevInter].as<double2>();
     PaletteDev pd;
     pd.sums = (unsigned long long*)dw;
     pd.hist = (unsigned*)(dw + 256);
@@ -226,9 +227,8 @@ extern "C" int phd_debug_time_kernel(int kernel, const uint8_t* d_rgb, int heigh
         hipMalloc(&cscratch, sizeof(double) * ((size_t)nbins + std::max(4096, fs.col_blocks))) != hipSuccess)
         return -1;
     FreeOnExit free_cscratch{cscratch};
-    const uint8_t** d_ptr = nullptr;
-    if (!ensure_device((void**)&c->d_ptrs, &c->ptrs_bytes, sizeof(void*))) return -1;
-    d_ptr = (const uint8_t**)c->d_ptrs;
+    if (!c->dev[kDevPtrs].ensure(sizeof(void*))) return -1;
+    const uint8_t** d_ptr = c->dev[kDevPtrs].as<const uint8_t*>();
     if (hipMemcpy(d_ptr, &d_rgb, sizeof(void*), hipMemcpyHostToDevice) != hipSuccess) return -1;
     g_ablate = ablate;
     const hipStream_t st = c->stream;
@@ -244,8 +244,8 @@ extern "C" int phd_debug_time_kernel(int kernel, const uint8_t* d_rgb, int heigh
                                                     c->d_k255, kernel == kK1, kernel == kK1 && fused,
                                                     all_aligned(&d_rgb, 1), st);
                 break;
-            case kFftRows: e = launch_rows_sel(fs, d_rgb, height, width, pd.sums, c->d_k255, c->d_inter, st); break;
-            case kFftCols: e = launch_cols_sel(fs, c->d_inter, height, width, wf, tbl->d_map, nbins,
+            case kFftRows: e = launch_rows_sel(fs, d_rgb, height, width, pd.sums, c->d_k255, inter, st); break;
+            case kFftCols: e = launch_cols_sel(fs, inter, height, width, wf, tbl->d_map, nbins,
                                                (unsigned long long*)cscratch, (double*)cscratch + nbins, pd.sums,
                                                nullptr, st); break;
             default: set_error("kernel not supported by the timing hook"); g_ablate = 0; return -1;
@@ -319,15 +319,16 @@ extern "C" int phd_debug_power_spectrum(const uint8_t* d_rgb, int height, int wi
         return -2;
     }
     // the report just run left the image's channel sums at the start of the workspace
-    uint8_t* dw = (uint8_t*)c->d_ws;
+    uint8_t* dw = c->dev[kDevWs].as<uint8_t>();
+    double2* const inter = c->dev[kDevInter].as<double2>();
     const int wf = width / 2 + 1;
     double* scratch = nullptr;
     if (hipMalloc(&scratch, sizeof(double) * (nbins + std::max(4096, fs.col_blocks))) != hipSuccess) return -1;
     auto* scratch_bins = reinterpret_cast<unsigned long long*>(scratch);
     const hipStream_t st = c->stream;
-    hipError_t e = launch_rows_sel(fs, d_rgb, height, width, (const unsigned long long*)dw, c->d_k255, c->d_inter, st);
+    hipError_t e = launch_rows_sel(fs, d_rgb, height, width, (const unsigned long long*)dw, c->d_k255, inter, st);
     if (e == hipSuccess)
-        e = launch_cols_sel(fs, c->d_inter, height, width, wf, tbl->d_map, nbins, scratch_bins, scratch + nbins,
+        e = launch_cols_sel(fs, inter, height, width, wf, tbl->d_map, nbins, scratch_bins, scratch + nbins,
                             (const unsigned long long*)dw, d_out, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     (void)hipFree(scratch);

@@ -24,15 +24,16 @@ static Full_Report_Data* report_from_host(const uint8_t* rgb, int height, int wi
     std::lock_guard<std::mutex> lk(c->mu);
     const size_t row = 3 * (size_t)width;
     const size_t bytes = row * height;
-    if (!ensure_device((void**)&c->d_stage, &c->stage_bytes, bytes) || !upload_init(c)) return nullptr;
+    if (!c->dev[kDevStage].ensure(bytes) || !upload_init(c)) return nullptr;
+    uint8_t* const d_stage = c->dev[kDevStage].as<uint8_t>();
     if (row_stride == 0 || row_stride == row) {
         std::string why;
-        if (!upload_async(c, c->d_stage, rgb, bytes, &why)) {
+        if (!upload_async(c, d_stage, rgb, bytes, &why)) {
             set_error(why);
             return nullptr;
         }
     } else {
-        const hipError_t e = hipMemcpy2DAsync(c->d_stage, row, rgb, row_stride, row, height, hipMemcpyHostToDevice,
+        const hipError_t e = hipMemcpy2DAsync(d_stage, row, rgb, row_stride, row, height, hipMemcpyHostToDevice,
                                               c->h2d);
         if (e != hipSuccess) {
             set_error(std::string("upload failed: ") + hipGetErrorString(e));
@@ -43,7 +44,7 @@ static Full_Report_Data* report_from_host(const uint8_t* rgb, int height, int wi
         set_error("upload ordering failed");
         return nullptr;
     }
-    const uint8_t* imgs[1] = {c->d_stage};
+    const uint8_t* imgs[1] = {d_stage};
     Full_Report_Data* out = nullptr;
     int status = -1;
     run_reports(c, imgs, 1, height, width, *cfg, crops, &out, &status, nullptr);
@@ -171,10 +172,9 @@ extern "C" int phd_hsv_stats_batch_device(const uint8_t* d_rgb, int n_images, in
     const size_t a_stride = a_kd + al(256 * sizeof(unsigned long long));
     const size_t rec = (size_t)n_images * a_stride, ptrs = al(sizeof(void*) * (size_t)n_images);
     const size_t fin = (size_t)n_images * 8 * sizeof(unsigned long long);   // k_stats_finish's records
-    if (!ensure_device(&c->d_ws, &c->ws_bytes, rec + ptrs + fin) || !ensure_pinned(c, rec + ptrs + fin))
-        return -1;
-    uint8_t* dw = (uint8_t*)c->d_ws;
-    uint8_t* hp = (uint8_t*)c->h_pin;
+    if (!c->dev[kDevWs].ensure(rec + ptrs + fin) || !c->pin.ensure(rec + ptrs + fin)) return -1;
+    uint8_t* dw = c->dev[kDevWs].as<uint8_t>();
+    uint8_t* hp = c->pin.as<uint8_t>();
     const uint8_t** hptr = (const uint8_t**)(hp + rec);
     for (int i = 0; i < n_images; i++) hptr[i] = d_rgb + (size_t)i * stride;
     const GridParams gp = make_grid([] { phd_config d; phd_config_default(&d); return d; }());
@@ -242,12 +242,12 @@ static int blur_run(Context* c, int lanes, const uint8_t* const* imgs, int n_ima
     const size_t rb = r_kd + al(256 * sizeof(unsigned long long));
     const size_t ptrs = al(sizeof(void*) * (size_t)n_images);
     const size_t inter_one = sizeof(double2) * inter_elems(height, width);
-    if (!ensure_device(&c->d_ws, &c->ws_bytes, (size_t)n_images * rb + ptrs) ||
-        !ensure_pinned(c, (size_t)n_images * rb + ptrs) ||
-        !ensure_device((void**)&c->d_inter, &c->inter_bytes, inter_one))
+    if (!c->dev[kDevWs].ensure((size_t)n_images * rb + ptrs) || !c->pin.ensure((size_t)n_images * rb + ptrs) ||
+        !c->dev[kDevInter].ensure(inter_one))
         return -1;
-    uint8_t* dw = (uint8_t*)c->d_ws;
-    uint8_t* hp = (uint8_t*)c->h_pin;
+    uint8_t* dw = c->dev[kDevWs].as<uint8_t>();
+    uint8_t* hp = c->pin.as<uint8_t>();
+    double2* const inter = c->dev[kDevInter].as<double2>();
     auto fail = [&](hipError_t e, const char* what) {
         set_error(std::string("phd_blur_batch_device: ") + what + ": " + hipGetErrorString(e));
         return -1;
@@ -276,12 +276,12 @@ static int blur_run(Context* c, int lanes, const uint8_t* const* imgs, int n_ima
     for (int i = 0; i < n_images; i++) {
         unsigned long long* sums = (unsigned long long*)(dw + (size_t)i * rb + r_sums);
         int ps = c->prof.begin(kFftRows, st);
-        if ((e = launch_rows_sel(fs, imgs[i], height, width, sums, c->d_k255, c->d_inter, st,
+        if ((e = launch_rows_sel(fs, imgs[i], height, width, sums, c->d_k255, inter, st,
                                  fs.ct ? sums : nullptr)) != hipSuccess)
             return fail(e, "row pass");
         c->prof.end(ps, st);
         ps = c->prof.begin(kFftCols, st);
-        if ((e = launch_cols_sel(fs, c->d_inter, height, width, wf, tbl->d_map, nbins,
+        if ((e = launch_cols_sel(fs, inter, height, width, wf, tbl->d_map, nbins,
                                  (unsigned long long*)(dw + (size_t)i * rb + r_bins),
                                  (double*)(dw + (size_t)i * rb + r_fmax),
                                  sums, nullptr, st)) != hipSuccess)
@@ -375,22 +375,23 @@ static int report_batch_u8(const uint8_t* const* images, const int* heights, con
     size_t need = 0;
     for (const auto& g : groups) need = std::max(need, g.size() * 3 * (size_t)widths[g[0]] * heights[g[0]]);
     for (int b = 0; b < 2 && !groups.empty(); b++)
-        if (!ensure_device((void**)&c->d_stage2[b], &c->stage2_bytes[b], need)) return -1;
+        if (!c->dev[kDevStage2 + b].ensure(need)) return -1;
     struct Up {
         bool ok = true;
         std::string why;
     };
     auto upload = [c, images, heights, widths](const std::vector<int>& g, int b, Up* u) {
         const size_t bytes = 3 * (size_t)widths[g[0]] * heights[g[0]];
+        uint8_t* const stage2 = c->dev[kDevStage2 + b].as<uint8_t>();
         if (upload_streams() == 2 && g.size() > 1) {
             // odd images on h2d2 from a second thread: two pageable copies in flight
             Up u2;
             std::thread t2([&] {
                 for (size_t k = 1; k < g.size() && u2.ok; k += 2)
-                    u2.ok = upload_async(c, c->d_stage2[b] + k * bytes, images[g[k]], bytes, &u2.why, c->h2d2);
+                    u2.ok = upload_async(c, stage2 + k * bytes, images[g[k]], bytes, &u2.why, c->h2d2);
             });
             for (size_t k = 0; k < g.size() && u->ok; k += 2)
-                u->ok = upload_async(c, c->d_stage2[b] + k * bytes, images[g[k]], bytes, &u->why, c->h2d);
+                u->ok = upload_async(c, stage2 + k * bytes, images[g[k]], bytes, &u->why, c->h2d);
             t2.join();
             if (u->ok && !u2.ok) *u = u2;
             if (u->ok && (hipEventRecord(c->ev_h2d2, c->h2d2) != hipSuccess ||
@@ -400,7 +401,7 @@ static int report_batch_u8(const uint8_t* const* images, const int* heights, con
             }
         } else {
             for (size_t k = 0; k < g.size() && u->ok; k++)
-                u->ok = upload_async(c, c->d_stage2[b] + k * bytes, images[g[k]], bytes, &u->why);
+                u->ok = upload_async(c, stage2 + k * bytes, images[g[k]], bytes, &u->why);
         }
         if (u->ok && hipEventRecord(c->ev_up[b], c->h2d) != hipSuccess) {
             u->ok = false;
@@ -422,7 +423,7 @@ static int report_batch_u8(const uint8_t* const* images, const int* heights, con
         std::vector<const uint8_t*> ptrs(m);
         std::vector<const Crop_Boundaries*> cr(m, nullptr);
         for (int k = 0; k < m; k++) {
-            ptrs[k] = c->d_stage2[b] + (size_t)k * bytes;
+            ptrs[k] = c->dev[kDevStage2 + b].as<uint8_t>() + (size_t)k * bytes;
             if (crops) cr[k] = crops[g[k]];
         }
         RunResults r(m);
@@ -750,17 +751,17 @@ extern "C" int phd_sharpness_batch_device(const uint8_t* d_rgb, int n_images, in
     const size_t stride = image_stride ? image_stride : 3 * (size_t)width * height;
     std::vector<const uint8_t*> imgs(n_images);
     for (int i = 0; i < n_images; i++) imgs[i] = d_rgb + (size_t)i * stride;
-    if (!ensure_pinned(c, 2 * sizeof(double) * nb)) return -1;
+    if (!c->pin.ensure(2 * sizeof(double) * nb)) return -1;
     double* d_flat = nullptr;
     if (!enqueue_sharpness(c, imgs.data(), n_images, width, plan, nullptr, 0, st, &d_flat)) return -1;
     hipError_t e;
-    if ((e = hipMemcpyAsync(c->h_pin, d_flat, 2 * sizeof(double) * nb, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+    if ((e = hipMemcpyAsync(c->pin.as(), d_flat, 2 * sizeof(double) * nb, hipMemcpyDeviceToHost, st)) != hipSuccess ||
         (e = hipStreamSynchronize(st)) != hipSuccess) {
         set_error(std::string("phd_sharpness_batch_device: ") + hipGetErrorString(e));
         return -1;
     }
     c->prof.collect();
-    const double* sums = (const double*)c->h_pin;
+    const double* sums = c->pin.as<const double>();
     for (size_t k = 0; k < nb; k++) {
         const SharpBox& b = plan.boxes[k];
         out[k] = sharp_value(sums[2 * k], sums[2 * k + 1], b.right - b.left, b.bottom - b.top);

@@ -165,8 +165,8 @@ bool select_generic(Context* c, int height, int width, int nbins, FftSel* s) {
     // scratch reuses it (Z is consumed by the split before they run)
     const size_t rows = (size_t)hp * width + gfft_scratch_elems(*s->grow, hp);
     const size_t cols = s->gcol ? gfft_scratch_elems(*s->gcol, wf) : 0;
-    if (!ensure_device((void**)&c->d_gbuf, &c->gbuf_bytes, sizeof(double2) * std::max(rows, cols))) return false;
-    s->gbuf = c->d_gbuf;
+    if (!c->dev[kDevGbuf].ensure(sizeof(double2) * std::max(rows, cols))) return false;
+    s->gbuf = c->dev[kDevGbuf].as<double2>();
     return true;
 }
 

@@ -17,6 +17,7 @@
 #include "../../include/photohive_dsp.h"
 #include "phd_internal.h"
 #include "batch_plan.h"
+#include "grow_buf.h"
 #include "box_tiles.h"
 #include "box_stat_tiles.h"
 #include "sharp_plan.h"
@@ -201,6 +202,79 @@ void stop_copy_pool();
 int copy_pool_threads();
 int library_threads();    // lane worker + pool threads alive in this process
 
+// ---- the context's grow-only blocks (grow_buf.h) -------
+struct DeviceMem {
+    static void* alloc(size_t sz) { void* p = nullptr; return hipMalloc(&p, sz) == hipSuccess ? p : nullptr; }
+    static void free(void* p) { (void)hipFree(p); }
+    static void idle() { (void)hipDeviceSynchronize(); }
+    static void failed(size_t sz) { set_error("hipMalloc of " + std::to_string(sz) + " bytes failed"); }
+};
+struct PinnedMem : DeviceMem {                      // (idle: the device's, as pinned copies run on its streams)
+    static void* alloc(size_t sz) {
+        void* p = nullptr;
+        return hipHostMalloc(&p, sz, hipHostMallocDefault) == hipSuccess ? p : nullptr;
+    }
+    static void free(void* p) { (void)hipHostFree(p); }
+    static void failed(size_t) { set_error("hipHostMalloc failed"); }
+};
+using DevBuf = GrowBuf<DeviceMem>;
+using PinBuf = GrowBuf<PinnedMem>;
+// A stage's pair and its two copies on st.  Stream order makes the one pinned block
+// serve both ways: the table has gone up (and been read) before a copy later on st
+// overwrites it; no copy of an earlier call is in flight when reserve() regrows (GrowBuf).
+struct Staged : StagedBuf<DeviceMem, PinnedMem> {
+    bool up(size_t bytes, hipStream_t st) {          // the first `bytes` of h to the start of d
+        PHD_HIP(hipMemcpyAsync(d.as(), h.as(), bytes, hipMemcpyHostToDevice, st));
+        return true;
+    }
+    bool down(size_t dev_off, size_t bytes, hipStream_t st, size_t pin_off = 0) {   // d + dev_off to h (+ pin_off)
+        PHD_HIP(hipMemcpyAsync(h.as<char>() + pin_off, d.as<char>() + dev_off, bytes, hipMemcpyDeviceToHost, st));
+        return true;
+    }
+};
+// Context::dev[]
+enum DevBufId {
+    kDevGbuf,                                   // generic 2-D path: row pairs + scratch (double2)
+    kDevPlanes,                                 // planar input: r | g | b | luma (fp64)
+    kDevPrec,                                   // planar input: per-call records
+    kDevWs,                                     // run_reports' workspace (its pinned twin: pin)
+    kDevInter,                                  // the half spectra between the FFT passes (double2)
+    kDevStage,                                  // upload staging for host images
+    kDevPtrs,                                   // small device pointer arrays (debug hooks)
+    // the input stage (phd_inputs.cpp): the packed staging images of one run
+    // of views, typed views or YUV views
+    kDevVstage,
+    // the label maps of a run's images that have boxes to count and no map of
+    // the caller's: 2 * mh * mw bytes each at 256-byte steps
+    kDevLabScratch,
+    kDevStage2, kDevStage2b,                    // host-buffer uploads: staging of overlapping groups
+    kNumDevBufs
+};
+// Context::staged[]
+enum StagedId {
+    // batched sharpness (sharp_tiles.h): device pointers | box table | prefix |
+    // slice partials (| flat sums), and the pinned copy of the uploaded part
+    kStSharp,
+    // the input stage: the device table of the pack, classify or conversion
+    // launch and its pinned copy; ev_views follows the last such launch (the
+    // table is rewritten only after it).  The label map launches' tables go
+    // through the same pair (upload_table)
+    kStViews,
+    // box palettes (phd_boxpal.cpp): the counters of a launch's boxes and
+    // their pinned copy
+    kStBoxPal,
+    // box statistics (phd_boxstats.cpp): records | items | the boxes' sums | the
+    // finish's 64 bytes per box on the device, and the pinned block the table
+    // goes up from and those 64 bytes come down to (the fp64 route: its items
+    // and partial sums through the same pair)
+    kStBoxStat,
+    // window blur (phd_blurwin.cpp): twiddles | window records | a chunk's bin
+    // sums | its maxima on the device, and the pinned block the table goes up
+    // from and a chunk's sums and maxima come down to
+    kStWinBlur,
+    kNumStaged
+};
+
 struct Context {
     int device = -1;
     pid_t pid = 0;                                  // the process that created it (phd_shutdown)
@@ -211,12 +285,6 @@ struct Context {
     std::map<std::tuple<int, int, int, int>, BlurTable> tables;
     std::map<std::tuple<int, int, int, int, int>, ColRuns> colruns;  // (H, W, nr, na, T): full-table runs
     std::map<int, GfftPlan> gplans;                 // global-memory FFT plans by length
-    double2* d_gbuf = nullptr;                      // generic 2-D path: row pairs + scratch
-    size_t gbuf_bytes = 0;
-    double* d_planes = nullptr;                     // planar input: r | g | b | luma (fp64)
-    size_t planes_bytes = 0;
-    void* d_prec = nullptr;                         // planar input: per-call records
-    size_t prec_bytes = 0;
     struct Cls {
         FastCls fc;
         ClassTables* d = nullptr;
@@ -227,59 +295,11 @@ struct Context {
     // grow-only workspaces
     std::vector<PaletteDecision> dec_scratch;       // run_reports' per-image decisions
     std::vector<std::vector<double>> hsum_scratch;  // and host slot sums
-    void* d_ws = nullptr;
-    size_t ws_bytes = 0;
-    void* h_pin = nullptr;
-    size_t pin_bytes = 0;
-    double2* d_inter = nullptr;
-    size_t inter_bytes = 0;
-    uint8_t* d_stage = nullptr;                    // upload staging for host images
-    void* d_ptrs = nullptr;                        // small device pointer arrays (debug hooks)
-    size_t ptrs_bytes = 0;
-    size_t stage_bytes = 0;
-    // batched sharpness (sharp_tiles.h): device pointers | box table | prefix |
-    // slice partials (| flat sums), and the pinned copy of the uploaded part
-    void* d_sharp = nullptr;
-    size_t sharp_bytes = 0;
-    void* h_sharp = nullptr;
-    size_t h_sharp_bytes = 0;
-    // the input stage (phd_inputs.cpp): the packed staging images of one run
-    // of views, typed views or YUV views, the device table of the pack,
-    // classify or conversion launch and its pinned copy; ev_views follows the
-    // last such launch (the table is rewritten only after it).  The label map
-    // launches' tables go through the same pair (upload_table)
-    uint8_t* d_vstage = nullptr;
-    size_t vstage_bytes = 0;
-    void* d_views = nullptr;
-    size_t views_bytes = 0;
-    void* h_views = nullptr;
-    size_t h_views_bytes = 0;
+    // grow-only blocks: freed and counted in loops (destroy_context, phd_debug_context_bytes)
+    DevBuf dev[kNumDevBufs];
+    Staged staged[kNumStaged];
+    PinBuf pin;
     hipEvent_t ev_views = nullptr;
-    // box palettes (phd_boxpal.cpp): the counters of a launch's boxes and
-    // their pinned copy
-    void* d_boxpal = nullptr;
-    size_t boxpal_bytes = 0;
-    void* h_boxpal = nullptr;
-    size_t h_boxpal_bytes = 0;
-    // box statistics (phd_boxstats.cpp): records | items | the boxes' sums | the
-    // finish's 64 bytes per box on the device, and the pinned block the table
-    // goes up from and those 64 bytes come down to (the fp64 route: its items
-    // and partial sums through the same pair)
-    void* d_boxstat = nullptr;
-    size_t boxstat_bytes = 0;
-    void* h_boxstat = nullptr;
-    size_t h_boxstat_bytes = 0;
-    // window blur (phd_blurwin.cpp): twiddles | window records | a chunk's bin
-    // sums | its maxima on the device, and the pinned block the table goes up
-    // from and a chunk's sums and maxima come down to
-    void* d_winblur = nullptr;
-    size_t winblur_bytes = 0;
-    void* h_winblur = nullptr;
-    size_t h_winblur_bytes = 0;
-    // the label maps of a run's images that have boxes to count and no map of
-    // the caller's: 2 * mh * mw bytes each at 256-byte steps, grow-only
-    void* d_labscratch = nullptr;
-    size_t labscratch_bytes = 0;
     // typed views: the snap tables' device copy (views_plan.h: snap_tables)
     uint8_t* d_snap = nullptr;
     hipEvent_t ev[8] = {};
@@ -304,8 +324,6 @@ struct Context {
     std::vector<char> slot_used;
     int next_slot = 0;
     hipEvent_t ev_up[2] = {};
-    uint8_t* d_stage2[2] = {};
-    size_t stage2_bytes[2] = {};
     std::mutex mu;
 };
 // The context of the current HIP device (created on first use).  nullptr if no GPU.
@@ -356,8 +374,6 @@ hipStream_t work_stream(Context* c, void* stream);
 // workspace records start at 256-byte steps
 constexpr size_t kAlign = 256;
 inline size_t al(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
-bool ensure_device(void** p, size_t* cap, size_t need);
-bool ensure_pinned(Context* c, size_t need);
 const FftPlanHost* get_plan(Context* c, int n, bool composite = false);
 // Per-pass twiddle tables of the compile-time plan of length n (rows or columns).
 const double2* get_ct_twiddles(Context* c, int n, bool rows);
@@ -451,7 +467,7 @@ struct ImageOutputs {
     uint16_t* labels = nullptr;
     // the caller's struct (zeroed by the entry): n_slots of a reported image and
     // the counts of its boxes, from labels or from a scratch map of the context
-    // (Context::d_labscratch); a failed image keeps {0, 0, NULL}
+    // (kDevLabScratch); a failed image keeps {0, 0, NULL}
     phd_box_palette* box_pal = nullptr;
     // the caller's struct (zeroed by the entry): the statistics of its boxes at
     // full resolution; a failed image and one without boxes keep {0, NULL, NULL}
@@ -478,7 +494,7 @@ struct CallOutputs {
     bool needs_label_slots() const { return d_labels || box_palettes; }
 };
 // report_planar after its upload: the fp64 planar pipeline on planes already
-// in c->d_planes (4 n doubles: P.r | P.g | P.b | luma) on the idle stream st;
+// in kDevPlanes (4 n doubles: P.r | P.g | P.b | luma) on the idle stream st;
 // cfg, the size and the boxes validated by the caller.  The typed entry runs
 // it on the planes k_decode_view filled.  outs: ImageOutputs, the box
 // statistics from the fp64 functions on the planes (k_planar_box_stats).
@@ -495,10 +511,10 @@ bool run_reports(Context* c, const uint8_t* const* d_imgs, int n, int height, in
                  const phd_config& cfg, const Crop_Boundaries* crops, Full_Report_Data** out,
                  int* status, hipStream_t stream, const Crop_Boundaries* const* img_crops = nullptr,
                  const ImageOutputs* outs = nullptr);
-// A launch table (phd_inputs.cpp): `bytes` go up on st into Context::d_views
-// from its pinned copy Context::h_views.  table_begin returns that pinned block
-// (nullptr: error) once the last launch that read the table is done, to be
-// filled in place -- Context::d_views has its final address by then;
+// A launch table (phd_inputs.cpp): `bytes` go up on st through the kStViews
+// pair.  table_begin returns its pinned block (nullptr: error) once the last
+// launch that read the table is done, to be filled in place -- the device
+// block has its final address by then;
 // table_upload is the one copy; table_launched: after the last operation on st
 // that reads the table.  upload_table: the three steps with the first `filled`
 // bytes from `host`, the rest zero.
@@ -518,7 +534,7 @@ bool table_call(Context* c, void* stream, size_t bytes, Fill fill, Launch launch
     fill(h);
     if (!table_upload(c, bytes, st)) return false;
     const int ps = c->prof.begin(slot, st);
-    const hipError_t e = launch((const uint8_t*)c->d_views, st);
+    const hipError_t e = launch(c->staged[kStViews].d.as<const uint8_t>(), st);
     c->prof.end(ps, st);
     PHD_HIP(e);
     if (!table_launched(c, st)) return false;
@@ -547,9 +563,9 @@ struct BoxJob {
     void add_image(const uint16_t* map, int mh, int mw, int ds, int n_slots, const Crop_Boundaries* b);
 };
 bool box_palette_fill(phd_box_palette* bp, int n_boxes, int n_slots, const uint32_t* h);
-// The job on st: its table goes up (table_begin), Context::d_boxpal is zeroed
+// The job on st: its table goes up (table_begin), kStBoxPal's device block is zeroed
 // by one memset, one launch counts, one copy brings the counters to
-// Context::h_boxpal.  The caller waits for st before it reads them.
+// its pinned block.  The caller waits for st before it reads them.
 bool enqueue_box_job(Context* c, const BoxJob& job, hipStream_t st);
 // The box statistics of a launch (phd_boxstats.cpp; records and row walk:
 // box_stat_tiles.h): the boxes' records and box_plan's items.
@@ -559,9 +575,9 @@ struct BoxStatJob {
     // the boxes of a packed RGB8 image of `width` columns (validated: crops_why)
     void add_image(const uint8_t* img, int width, const Crop_Boundaries* b);
 };
-// The job on st: the table goes up from Context::h_boxstat, one memset zeroes
+// The job on st: the table goes up through kStBoxStat, one memset zeroes
 // the records, k_box_stats (profile slot 12) and its finish run, one copy brings
-// kBoxStatOut u64 per box to Context::h_boxstat, where box_stats_host() points
+// kBoxStatOut u64 per box to its pinned block, where box_stats_host() points
 // after the caller has waited for st.
 bool enqueue_box_stat_job(Context* c, const BoxStatJob& job, hipStream_t st);
 const unsigned long long* box_stats_host(const Context* c);
@@ -570,8 +586,6 @@ const unsigned long long* box_stats_host(const Context* c);
 bool box_stats_fill(phd_box_stats* bs, const Crop_Boundaries* b, const unsigned long long* h);
 // the same from finished values: stats[k], average_saturation[k]
 bool box_stats_alloc(phd_box_stats* bs, int n_boxes);
-// A grow-only pinned block of at least `need` bytes (the old one is freed at once)
-bool grow_pinned(void** p, size_t* cap, size_t need);
 
 // ---- device batches (the driver: phd_entries.cpp; views, typed views and
 // ---- YUV views: phd_inputs.cpp) ------------------------------------------------

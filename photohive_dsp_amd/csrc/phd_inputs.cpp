@@ -16,7 +16,7 @@ namespace phd {
 
 // ---- launch tables ------------------------------------------------------------
 // `bytes` of a launch table go up on st from the context's pinned copy
-// (d_views / h_views).  The table of the context's last launch is still read
+// (kStViews).  The table of the context's last launch is still read
 // until that launch is done (a caller's stream is not drained by the call
 // that used it): ev_views, recorded by table_launched, is waited for first --
 // here and nowhere else.  The pinned block to fill, or nullptr.
@@ -24,16 +24,12 @@ void* table_begin(Context* c, size_t bytes) {
     auto ready = [&]() {
         if (!c->ev_views) PHD_HIP(hipEventCreateWithFlags(&c->ev_views, hipEventDisableTiming));
         else PHD_HIP(hipEventSynchronize(c->ev_views));
-        return ensure_device(&c->d_views, &c->views_bytes, bytes) &&
-               grow_pinned(&c->h_views, &c->h_views_bytes, bytes);
+        return c->staged[kStViews].reserve(bytes, bytes);
     };
-    return ready() ? c->h_views : nullptr;
+    return ready() ? c->staged[kStViews].h.as() : nullptr;
 }
 
-bool table_upload(Context* c, size_t bytes, hipStream_t st) {
-    PHD_HIP(hipMemcpyAsync(c->d_views, c->h_views, bytes, hipMemcpyHostToDevice, st));
-    return true;
-}
+bool table_upload(Context* c, size_t bytes, hipStream_t st) { return c->staged[kStViews].up(bytes, st); }
 
 // The first `filled` bytes from `host`, the rest zero.
 bool upload_table(Context* c, const void* host, size_t filled, size_t bytes, hipStream_t st) {
@@ -60,7 +56,7 @@ constexpr int kMaxViewsPerLaunch = 32768;
 // The launches of a non-empty table of records on st, in chunks of
 // kMaxViewsPerLaunch: launch(device records, first record's number, count,
 // max_bands).  `extra` zeroed bytes follow the records at the next 256-byte
-// step, *o_extra bytes into d_views / h_views.
+// step, *o_extra bytes into the kStViews pair.
 template <class Rec, class Launch>
 bool launch_views(Context* c, const std::vector<Rec>& recs, size_t extra, size_t* o_extra, hipStream_t st,
                   Launch launch) {
@@ -71,7 +67,7 @@ bool launch_views(Context* c, const std::vector<Rec>& recs, size_t extra, size_t
     if (!upload_table(c, recs.data(), filled, extra ? al(filled) + extra : filled, st)) return false;
     for (size_t k = 0; k < recs.size(); k += kMaxViewsPerLaunch) {
         const int m = (int)std::min<size_t>(kMaxViewsPerLaunch, recs.size() - k);
-        PHD_HIP(launch((const Rec*)c->d_views + k, k, m, max_bands));
+        PHD_HIP(launch(c->staged[kStViews].d.as<const Rec>() + k, k, m, max_bands));
     }
     return true;
 }
@@ -127,15 +123,14 @@ bool classify_views(Context* c, const phd_typed_view* views, uint8_t* const* dst
     for (int i = 0; i < n; i++) recs[i] = decode_record(views[i], nullptr, dst[i], snap);
     const size_t fbytes = sizeof(int) * (size_t)n;
     size_t o_flags = 0;
+    Staged& S = c->staged[kStViews];
     if (!launch_views(c, recs, fbytes, &o_flags, st, [&](const DecodeRec* d, size_t k, int m, int bands) {
-            return launch_classify_views(d, (int*)((uint8_t*)c->d_views + o_flags) + k, m, bands, st, &c->prof);
+            return launch_classify_views(d, (int*)(S.d.as<uint8_t>() + o_flags) + k, m, bands, st, &c->prof);
         }))
         return false;
-    PHD_HIP(hipMemcpyAsync((uint8_t*)c->h_views + o_flags, (uint8_t*)c->d_views + o_flags, fbytes,
-                           hipMemcpyDeviceToHost, st));
-    if (!table_launched(c, st)) return false;
+    if (!S.down(o_flags, fbytes, st, o_flags) || !table_launched(c, st)) return false;
     PHD_HIP(hipStreamSynchronize(st));
-    memcpy(flags, (uint8_t*)c->h_views + o_flags, fbytes);
+    memcpy(flags, S.h.as<uint8_t>() + o_flags, fbytes);
     return true;
 }
 
@@ -169,11 +164,11 @@ bool stage_slots(Context* cl, int height, int width, int gm, Needs needs, int na
     size_t staged = 0;
     for (int k = 0; k < gm; k++) staged += needs(k);
     // (every allocation before the first launch that writes into it)
-    if (staged && !ensure_device((void**)&cl->d_vstage, &cl->vstage_bytes, staged * step)) return false;
+    if (staged && !cl->dev[kDevVstage].ensure(staged * step)) return false;
     slots->assign(gm, nullptr);
     size_t slot = 0;
     for (int k = 0; k < gm; k++)
-        if (needs(k)) (*slots)[k] = cl->d_vstage + slot++ * step;
+        if (needs(k)) (*slots)[k] = cl->dev[kDevVstage].as<uint8_t>() + slot++ * step;
     return true;
 }
 
@@ -271,11 +266,11 @@ void run_typed_group(Context* cl, const std::vector<BatchImage>& imgs, const std
             continue;
         }
         // (the stream is idle: the planes may move)
-        if (!ensure_device((void**)&cl->d_planes, &cl->planes_bytes, sizeof(double) * 4 * n)) {
+        if (!cl->dev[kDevPlanes].ensure(sizeof(double) * 4 * n)) {
             bad = name + phd_last_error();
             continue;
         }
-        double* dp = cl->d_planes;
+        double* dp = cl->dev[kDevPlanes].as<double>();
         Full_Report_Data* o = nullptr;
         if (enqueue_decode_view(cl, tv(k), dp, st))
             o = report_planes_device(cl, PlanarSrc{dp, dp + n, dp + 2 * n}, height, width, cfg,

@@ -43,7 +43,7 @@ extern "C" int phd_labels_to_rgb_device(const uint16_t* const* d_labels, const i
     memset(tab, 0, rec_bytes);
     LabelRgbRec* recs = reinterpret_cast<LabelRgbRec*>(tab);
     unsigned* words = reinterpret_cast<unsigned*>(tab + rec_bytes);
-    const unsigned* d_words = reinterpret_cast<const unsigned*>((const uint8_t*)c->d_views + rec_bytes);
+    const unsigned* d_words = reinterpret_cast<const unsigned*>(c->staged[kStViews].d.as<const uint8_t>() + rec_bytes);
     const unsigned none = (unsigned)none_rgb[0] | (unsigned)none_rgb[1] << 8 | (unsigned)none_rgb[2] << 16;
     long max_npix = 0;
     size_t w = 0;
@@ -57,7 +57,7 @@ extern "C" int phd_labels_to_rgb_device(const uint16_t* const* d_labels, const i
     }
     auto run = [&]() {
         if (!table_upload(c, bytes, st)) return false;
-        PHD_HIP(launch_labels_to_rgb((const LabelRgbRec*)c->d_views, n_maps, max_npix, st));
+        PHD_HIP(launch_labels_to_rgb(c->staged[kStViews].d.as<const LabelRgbRec>(), n_maps, max_npix, st));
         if (!table_launched(c, st)) return false;
         if (!stream) PHD_HIP(hipStreamSynchronize(st));
         return true;

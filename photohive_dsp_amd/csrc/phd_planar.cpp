@@ -80,24 +80,24 @@ Full_Report_Data* report_planar(Context* c, const double* r, const double* g, co
     if (!precheck(height, width) || !check_crops(crops, height, width)) return nullptr;
     const long n = (long)height * width;
     const hipStream_t st = c->stream;
-    if (!ensure_device((void**)&c->d_planes, &c->planes_bytes, sizeof(double) * 4 * (size_t)n) ||
-        !ensure_device((void**)&c->d_stage, &c->stage_bytes, 3 * (size_t)n))
+    if (!c->dev[kDevPlanes].ensure(sizeof(double) * 4 * (size_t)n) || !c->dev[kDevStage].ensure(3 * (size_t)n))
         return nullptr;
-    double* dp = c->d_planes;
+    double* dp = c->dev[kDevPlanes].as<double>();
+    uint8_t* const d_stage = c->dev[kDevStage].as<uint8_t>();
     const PlanarSrc P{dp, dp + n, dp + 2 * n};
-    if (!ensure_device(&c->d_prec, &c->prec_bytes, kAlign)) return nullptr;
-    int* flags = (int*)c->d_prec;
+    if (!c->dev[kDevPrec].ensure(kAlign)) return nullptr;
+    int* flags = c->dev[kDevPrec].as<int>();
     PHD_HIPN(hipMemsetAsync(flags, 0, sizeof(int), st));
     PHD_HIPN(hipMemcpyAsync((void*)P.r, r, sizeof(double) * n, hipMemcpyHostToDevice, st));
     PHD_HIPN(hipMemcpyAsync((void*)P.g, g, sizeof(double) * n, hipMemcpyHostToDevice, st));
     PHD_HIPN(hipMemcpyAsync((void*)P.b, b, sizeof(double) * n, hipMemcpyHostToDevice, st));
-    PHD_HIPN(launch_planar_to_u8(P, n, c->d_stage, flags, st));
+    PHD_HIPN(launch_planar_to_u8(P, n, d_stage, flags, st));
     int hflags = 0;
     PHD_HIPN(hipMemcpyAsync(&hflags, flags, sizeof(int), hipMemcpyDeviceToHost, st));
     PHD_HIPN(hipStreamSynchronize(st));
     if (!(hflags & 1)) {
         // an 8-bit image: the RGB8 pipeline, exactly the reference's arithmetic on these doubles
-        const uint8_t* imgs[1] = {c->d_stage};
+        const uint8_t* imgs[1] = {d_stage};
         Full_Report_Data* out = nullptr;
         int status = -1;
         run_reports(c, imgs, 1, height, width, cfg, crops, &out, &status, nullptr);
@@ -112,7 +112,7 @@ Full_Report_Data* report_planar(Context* c, const double* r, const double* g, co
 
 // Everything after the upload: the fp64 planar pipeline on planes that are on
 // the device already -- P.r | P.g | P.b are the first 3 n doubles of
-// c->d_planes (4 n doubles), whose fourth plane takes the luma.  cfg, the size
+// kDevPlanes (4 n doubles), whose fourth plane takes the luma.  cfg, the size
 // and the boxes are validated; nothing but the planes' own producer is queued
 // on st (no buffer allocated here is in use).  outs (ImageOutputs, phd_host.h):
 // the label map is written on st behind the palette tail.
@@ -121,7 +121,7 @@ Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int heigh
     std::string why;
     uint16_t* labels = outs.labels;                          // (or a scratch map for the box counts)
     const long n = (long)height * width;
-    double* pgm = c->d_planes + 3 * n;
+    double* pgm = c->dev[kDevPlanes].as<double>() + 3 * n;
     const int nb = planar_blocks(n);
     const GridParams gp = make_grid(cfg);
     const int ds = cfg.downsample_rate > 1 ? cfg.downsample_rate : 1;
@@ -136,19 +136,21 @@ Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int heigh
     const Context::Cls* cls = get_cls(c, gp);
     if (!tbl || !cls) return nullptr;
     const PRec R = prec_layout(nb, gp.tl, nchunks, nbins, fs.col_blocks, ncrops);
-    if (!ensure_device(&c->d_prec, &c->prec_bytes, R.total) ||
-        !ensure_device((void**)&c->d_inter, &c->inter_bytes, sizeof(double2) * ((size_t)height * wf + 1024)))
+    if (!c->dev[kDevPrec].ensure(R.total) ||
+        !c->dev[kDevInter].ensure(sizeof(double2) * ((size_t)height * wf + 1024)))
         return nullptr;
+    double2* const inter = c->dev[kDevInter].as<double2>();
     // box palettes: the boxes are counted from the caller's map, or from one in the context's scratch
     const bool count_boxes = outs.box_pal && ncrops > 0;
     const int mh = ds > 1 ? height / ds : height, mw = ds > 1 ? width / ds : width;
     if (count_boxes && !labels) {
-        if (!ensure_device(&c->d_labscratch, &c->labscratch_bytes, sizeof(uint16_t) * (size_t)mh * mw)) return nullptr;
-        labels = (uint16_t*)c->d_labscratch;
+        if (!c->dev[kDevLabScratch].ensure(sizeof(uint16_t) * (size_t)mh * mw)) return nullptr;
+        labels = c->dev[kDevLabScratch].as<uint16_t>();
     }
     // box statistics: box_plan's bands as items; device: items | part1 | part2,
     // pinned: the items going up, then the two partial arrays coming down
     std::vector<PlanarBoxItem> bs_items;
+    Staged& BS = c->staged[kStBoxStat];
     size_t bs_o1 = 0, bs_o2 = 0;
     if (outs.box_stats && ncrops > 0) {
         std::vector<BoxItem> bands;
@@ -162,12 +164,11 @@ Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int heigh
         }
         bs_o1 = al(sizeof(PlanarBoxItem) * bs_items.size());
         bs_o2 = bs_o1 + al(sizeof(double) * 4 * bs_items.size());
-        if (!ensure_device(&c->d_boxstat, &c->boxstat_bytes, bs_o2 + sizeof(double) * 3 * bs_items.size()) ||
-            !grow_pinned(&c->h_boxstat, &c->h_boxstat_bytes,
-                         std::max(sizeof(PlanarBoxItem), sizeof(double) * 7) * bs_items.size()))
+        if (!BS.reserve(bs_o2 + sizeof(double) * 3 * bs_items.size(),
+                        std::max(sizeof(PlanarBoxItem), sizeof(double) * 7) * bs_items.size()))
             return nullptr;
     }
-    uint8_t* dr = (uint8_t*)c->d_prec;
+    uint8_t* dr = c->dev[kDevPrec].as<uint8_t>();
     int* flags = (int*)(dr + R.flags);
     PHD_HIPN(hipMemsetAsync(dr, 0, R.total, st));
     // ---- the fp64 planar pipeline -------------------------------------------------
@@ -203,8 +204,8 @@ Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int heigh
     // the blur profile on the luma plane while the host decides
     unsigned long long* bins = (unsigned long long*)(dr + R.bins);
     double* fmx = (double*)(dr + R.fmax);
-    PHD_HIPN(generic_rows(fs, nullptr, pgm, height, width, nullptr, avg, c->d_k255, c->d_inter, st));
-    PHD_HIPN(generic_cols(fs, c->d_inter, height, wf, tbl->d_map, nbins, bins, fmx, st, bscale));
+    PHD_HIPN(generic_rows(fs, nullptr, pgm, height, width, nullptr, avg, c->d_k255, inter, st));
+    PHD_HIPN(generic_cols(fs, inter, height, wf, tbl->d_map, nbins, bins, fmx, st, bscale));
     if (ncrops) {
         // get_variance_sharpness runs on the luma before the DC removal (src/interface.c:70-73)
         std::vector<int> ca(4 * ncrops);
@@ -221,17 +222,17 @@ Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int heigh
     if (!bs_items.empty()) {
         // the two launches of the fp64 box statistics and their one download each,
         // behind the sharpness crops; the host finishes after the call's last wait
-        uint8_t* db = (uint8_t*)c->d_boxstat;
-        double* hb = (double*)c->h_boxstat;
+        uint8_t* db = BS.d.as<uint8_t>();
         const size_t ni = bs_items.size();
-        memcpy(c->h_boxstat, bs_items.data(), sizeof(PlanarBoxItem) * ni);
-        PHD_HIPN(hipMemcpyAsync(db, c->h_boxstat, sizeof(PlanarBoxItem) * ni, hipMemcpyHostToDevice, st));
+        memcpy(BS.h.as(), bs_items.data(), sizeof(PlanarBoxItem) * ni);
+        if (!BS.up(sizeof(PlanarBoxItem) * ni, st)) return nullptr;
         const int ps = c->prof.begin(kPlanarBoxStats, st);
         PHD_HIPN(launch_planar_box_stats(P, width, (const PlanarBoxItem*)db, (int)ni, (double*)(db + bs_o1),
                                          (double*)(db + bs_o2), st));
         c->prof.end(ps, st);
-        PHD_HIPN(hipMemcpyAsync(hb, db + bs_o1, sizeof(double) * 4 * ni, hipMemcpyDeviceToHost, st));
-        PHD_HIPN(hipMemcpyAsync(hb + 4 * ni, db + bs_o2, sizeof(double) * 3 * ni, hipMemcpyDeviceToHost, st));
+        if (!BS.down(bs_o1, sizeof(double) * 4 * ni, st) ||
+            !BS.down(bs_o2, sizeof(double) * 3 * ni, st, sizeof(double) * 4 * ni))
+            return nullptr;
     }
     PHD_HIPN(hipEventSynchronize(c->ev[5]));
     const int hf = *(const int*)(h.data() + R.flags);
@@ -296,11 +297,12 @@ Full_Report_Data* report_planes_device(Context* c, const PlanarSrc& P, int heigh
                                      (const double*)(h.data() + R.sharp), &why, bscale);
     if (!out) set_error(why);
     else if (outs.box_pal)
-        (void)box_palette_fill(outs.box_pal, ncrops, (int)dec.parents.size(), (const uint32_t*)c->h_boxpal);
+        (void)box_palette_fill(outs.box_pal, ncrops, (int)dec.parents.size(),
+                               c->staged[kStBoxPal].h.as<const uint32_t>());
     if (out && !bs_items.empty() && box_stats_alloc(outs.box_stats, ncrops)) {
         // the items' partials in item order: B = sum / N as the device formed it,
         // C = sqrt(sum (x - B)^2 / N), S-bar = sum(s) / N
-        const double* p1 = (const double*)c->h_boxstat;
+        const double* p1 = BS.h.as<const double>();
         const double* p2 = p1 + 4 * bs_items.size();
         int box = 0;
         for (size_t q = 0; q < bs_items.size(); q += bs_items[q].count, box++) {

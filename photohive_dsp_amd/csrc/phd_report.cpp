@@ -79,21 +79,6 @@ Layout make_layout(int n, int tl, int nchunks, int nbins, int ncrops, int ncolbl
 
 }  // namespace
 
-// (phd_host.h; the sharpness box table here, the input stage's launch tables)
-bool grow_pinned(void** p, size_t* cap, size_t need) {
-    if (*cap >= need) return true;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    const size_t sz = need + need / 4 + 4096;
-    if (hipHostMalloc(p, sz, hipHostMallocDefault) != hipSuccess) {
-        set_error("hipHostMalloc failed");
-        return false;
-    }
-    *cap = sz;
-    return true;
-}
-
 // shared with the planar path (phd_planar.cpp)
 bool check_crops(const Crop_Boundaries* cb, int height, int width) {
     // the rules: crops_why (phd_sharp_host.cpp)
@@ -115,15 +100,14 @@ bool enqueue_sharpness(Context* c, const uint8_t* const* d_imgs, int n, int widt
     const size_t up = o_pre + al(sizeof(int) * ((size_t)nb + 1));
     const size_t o_flat = up + al(sizeof(SharpPart) * (size_t)nslices);
     const size_t total = o_flat + (out0 ? 0 : al(2 * sizeof(double) * (size_t)nb));
-    if (!ensure_device(&c->d_sharp, &c->sharp_bytes, total)) return false;
-    // (every call drains its streams before it returns: no copy reads the old block)
-    if (!grow_pinned(&c->h_sharp, &c->h_sharp_bytes, up)) return false;
-    uint8_t* hs = (uint8_t*)c->h_sharp;
-    uint8_t* ds = (uint8_t*)c->d_sharp;
+    Staged& S = c->staged[kStSharp];
+    if (!S.reserve(total, up)) return false;
+    uint8_t* hs = S.h.as<uint8_t>();
+    uint8_t* ds = S.d.as<uint8_t>();
     memcpy(hs, d_imgs, sizeof(void*) * (size_t)n);
     memcpy(hs + o_box, plan.boxes.data(), sizeof(SharpBox) * (size_t)nb);
     memcpy(hs + o_pre, plan.prefix.data(), sizeof(int) * ((size_t)nb + 1));
-    PHD_HIP(hipMemcpyAsync(ds, hs, up, hipMemcpyHostToDevice, st));
+    if (!S.up(up, st)) return false;
     double* dst = out0 ? out0 : (double*)(ds + o_flat);
     if (flat_dev) *flat_dev = dst;
     PHD_HIP(launch_sharpness_batch((const uint8_t* const*)ds, (const SharpBox*)(ds + o_box), (const int*)(ds + o_pre),
@@ -189,8 +173,8 @@ void fill_b_record(const Layout& L, const PaletteDecision& dec, int tl, uint8_t*
 // pointer array staged in the workspace, or per-image launches (ds > 1).
 bool launch_k1(Context* c, const Layout& L, int n, const uint8_t* const* d_imgs, int height, int width, int ds,
                const GridParams& gp, const Context::Cls* cls, int nchunks, bool fused, hipStream_t st) {
-    uint8_t* dw = (uint8_t*)c->d_ws;
-    uint8_t* hp = (uint8_t*)c->h_pin;
+    uint8_t* dw = c->dev[kDevWs].as<uint8_t>();
+    uint8_t* hp = c->pin.as<uint8_t>();
     PaletteDev pd = palette_dev(dw, L, n, 0);
     pd.gsum = (double*)(dw + L.A(0) + L.a_gsum);
     pd.gcell = (unsigned*)(dw + L.A(0) + L.a_gcell);
@@ -277,8 +261,8 @@ bool launch_palette_tail(Context* c, const Layout& L, int n, const uint8_t* cons
                          int ds, const GridParams& gp, const Context::Cls* cls, int nchunks, bool fused,
                          const PaletteDecision* dec, const int* ok, int n_ent, int max_slots, int max_per_img,
                          hipStream_t s2) {
-    uint8_t* dw = (uint8_t*)c->d_ws;
-    const uint8_t* hb = (const uint8_t*)c->h_pin + L.B(n, 0);
+    uint8_t* dw = c->dev[kDevWs].as<uint8_t>();
+    const uint8_t* hb = c->pin.as<uint8_t>() + L.B(n, 0);
     const bool batched = palette_tail_batched(gp, ds, fused, max_slots);
     // the B records (and, batched, the Kcut list right after them): one copy
     PHD_HIP(hipMemcpyAsync(dw + L.B(n, 0), hb, (size_t)n * L.b_bytes + (batched ? L.e_bytes : 0),
@@ -417,7 +401,7 @@ struct ReportRun : ReportArgs {
     bool label_maps();                                        // palette_tail()'s last step: maps and box counts
     bool label_launches(const std::vector<LabelDst>& dst, bool aligned);
     // box palettes: image i's boxes are counted (it has a decision, a struct
-    // and boxes); where its counters start in Context::h_boxpal (-1: none)
+    // and boxes); where its counters start in kStBoxPal's pinned block (-1: none)
     bool counts_boxes(int i) const {
         return o(i).box_pal && ok[i] && img_crops && img_crops[i] && img_crops[i]->N > 0;
     }
@@ -532,11 +516,11 @@ bool ReportRun::plan() {
     // event, one download and one host wait per group (small images were
     // bound by ~3 HIP calls and a wait per pair of images: DESIGN.md section 12)
     dlg = chain == FftChain::kPerImage ? dl_group : Q;
-    if (!ensure_device(&c->d_ws, &c->ws_bytes, L.dev_total) || !ensure_pinned(c, L.pin_total) ||
-        !ensure_device((void**)&c->d_inter, &c->inter_bytes, (size_t)Q * inter_one))
+    if (!c->dev[kDevWs].ensure(L.dev_total) || !c->pin.ensure(L.pin_total) ||
+        !c->dev[kDevInter].ensure((size_t)Q * inter_one))
         return false;
-    dw = (uint8_t*)c->d_ws;
-    hp = (uint8_t*)c->h_pin;
+    dw = c->dev[kDevWs].as<uint8_t>();
+    hp = c->pin.as<uint8_t>();
     if (ncrops) {
         crop_arr.resize(4 * ncrops);
         for (int k = 0; k < ncrops; k++) {
@@ -593,6 +577,7 @@ bool ReportRun::fft_chain() {
     if (any(&ImageOutputs::box_stats) && !box_stat_job()) return false;
     const uint8_t* const* d_ptrs = (const uint8_t* const*)(dw + L.P_dev(n));
     const long a_stride = (long)(L.a_bytes / 8), c_stride = (long)(L.c_bytes / 8);
+    double2* const inter = c->dev[kDevInter].as<double2>();
     for (int g0 = 0; g0 < n; g0 += Q) {
         const int g1 = std::min(n, g0 + Q), m = g1 - g0;
         const unsigned long long* sums = (const unsigned long long*)(dw + L.A(g0) + L.a_sums);
@@ -602,19 +587,19 @@ bool ReportRun::fft_chain() {
         int ps = c->prof.begin(kFftRows, sf);
         if (chain == FftChain::kRuntimeBatch)
             PHD_HIP(launch_fft_rows_batch(d_ptrs + g0, m, height, width, fs.prow->plan, sums, a_stride, c->d_k255,
-                                          c->d_inter, inter_elems, sf));
+                                          inter, inter_elems, sf));
         else if (chain == FftChain::kCtBatch)
-            PHD_HIP(launch_fft_rows_ct_batch(d_ptrs + g0, m, height, width, c->d_k255, fs.tw_r, c->d_inter,
+            PHD_HIP(launch_fft_rows_ct_batch(d_ptrs + g0, m, height, width, c->d_k255, fs.tw_r, inter,
                                              (long)inter_elems, sf));
         else   // (a per-image group is one image)
-            PHD_HIP(launch_rows_sel(fs, d_imgs[g0], height, width, sums, c->d_k255, c->d_inter, sf, nullptr));
+            PHD_HIP(launch_rows_sel(fs, d_imgs[g0], height, width, sums, c->d_k255, inter, sf, nullptr));
         c->prof.end(ps, sf);
         ps = c->prof.begin(kFftCols, sf);
         if (chain == FftChain::kRuntimeBatch) {
-            PHD_HIP(launch_fft_cols_batch(c->d_inter, inter_elems, m, height, wf, fs.pcol->plan, tbl->d_map, nbins,
+            PHD_HIP(launch_fft_cols_batch(inter, inter_elems, m, height, wf, fs.pcol->plan, tbl->d_map, nbins,
                                           bins, fmx, c_stride, sf));
         } else if (chain == FftChain::kCtBatch) {
-            PHD_HIP(launch_fft_cols_ct_batch(c->d_inter, (long)inter_elems, m, height, width, wf, fs.cbins, bins,
+            PHD_HIP(launch_fft_cols_ct_batch(inter, (long)inter_elems, m, height, width, wf, fs.cbins, bins,
                                              c_stride, fmx, c_stride, fs.tw_c, sums, a_stride, sf, fs.col_pf));
         } else {
             // an unprofiled column pass that ends a download group records the
@@ -624,7 +609,7 @@ bool ReportRun::fft_chain() {
             ArmedLaunchEvents own(fs.ct && ps < 0 && dl_end(g0) && !ncrops &&
                                       device_event_flags() == hipEventDisableSystemFence,
                                   nullptr, c->ev_img_fft[g0]);
-            PHD_HIP(launch_cols_sel(fs, c->d_inter, height, width, wf, tbl->d_map, nbins, bins, fmx, sums, nullptr,
+            PHD_HIP(launch_cols_sel(fs, inter, height, width, wf, tbl->d_map, nbins, bins, fmx, sums, nullptr,
                                     sf));
             recorded = own.used();
         }
@@ -740,7 +725,7 @@ bool ReportRun::palette_tail() {
 // the call's last download -- which the call waits for -- is behind the maps.
 //
 // Box palettes: an image whose boxes are counted and that has no map of the
-// caller's gets one in the context's scratch (d_labscratch: 2 * mh * mw bytes
+// caller's gets one in the context's scratch (kDevLabScratch: 2 * mh * mw bytes
 // per such image of the run at 256-byte steps), written by the same launches;
 // the counting launch and its one download (enqueue_box_job) follow them on
 // the tail stream, so the counters are on the host when the call's last
@@ -755,8 +740,8 @@ bool ReportRun::label_maps() {
         if (!map[i] && counts_boxes(i)) scratch += one;
     }
     if (scratch) {
-        if (!ensure_device(&c->d_labscratch, &c->labscratch_bytes, scratch)) return false;
-        uint8_t* p = (uint8_t*)c->d_labscratch;
+        if (!c->dev[kDevLabScratch].ensure(scratch)) return false;
+        uint8_t* p = c->dev[kDevLabScratch].as<uint8_t>();
         for (int i = 0; i < n; i++)
             if (!map[i] && counts_boxes(i)) {
                 map[i] = (uint16_t*)p;
@@ -790,7 +775,7 @@ bool ReportRun::label_launches(const std::vector<LabelDst>& dst, bool aligned) {
         PHD_HIP(launch_palette_labels_batch((const uint8_t* const*)(dw + L.P_dev(n)), aligned, height, width, gp,
                                             cls->fc, cls->d, c->d_k255,
                                             (const GroupRule*)(dw + L.B(n, 0) + L.b_rules), (long)L.b_bytes,
-                                            (const LabelDst*)c->d_views, (int)dst.size(), s2));
+                                            c->staged[kStViews].d.as<const LabelDst>(), (int)dst.size(), s2));
         c->prof.end(ps, s2);
         return table_launched(c, s2);
     }
@@ -924,7 +909,7 @@ bool ReportRun::timings() {
 }
 
 // The box palette structs of the reported images, from the counters the run's
-// streams brought to Context::h_boxpal (timings() has waited for them): n_slots
+// streams brought to kStBoxPal's pinned block (timings() has waited for them): n_slots
 // for each, the counts where the image has boxes.  A failed image keeps
 // {0, 0, NULL}.
 bool ReportRun::box_palettes() {
@@ -932,14 +917,14 @@ bool ReportRun::box_palettes() {
         if (!o(i).box_pal || !out[i]) continue;
         const bool counted = counts_boxes(i) && !bp_off.empty() && bp_off[i] >= 0;
         if (!box_palette_fill(o(i).box_pal, counted ? img_crops[i]->N : 0, (int)c->dec_scratch[i].parents.size(),
-                              counted ? (const uint32_t*)c->h_boxpal + bp_off[i] : nullptr))
+                              counted ? c->staged[kStBoxPal].h.as<const uint32_t>() + bp_off[i] : nullptr))
             return false;
     }
     return true;
 }
 
 // The box statistics structs of the reported images, from the 64 bytes per box
-// box_stat_job's download left in Context::h_boxstat (timings() has waited for
+// box_stat_job's download left in kStBoxStat's pinned block (timings() has waited for
 // it).  A failed image and an image without boxes keep {0, NULL, NULL}.
 bool ReportRun::box_statistics() {
     for (int i = 0; i < n; i++) {
@@ -974,9 +959,9 @@ bool run_palette_trace(Context* c, const uint8_t* d_img, int height, int width, 
     const long n_hsv = hsv_count(height, width, ds);
     const int nchunks = (int)((n_hsv + kChunk - 1) / kChunk);
     const Layout L = make_layout(1, gp.tl, nchunks, 1, 0, 1);
-    if (!ensure_device(&c->d_ws, &c->ws_bytes, L.dev_total) || !ensure_pinned(c, L.pin_total)) return false;
-    uint8_t* dw = (uint8_t*)c->d_ws;
-    uint8_t* hp = (uint8_t*)c->h_pin;
+    if (!c->dev[kDevWs].ensure(L.dev_total) || !c->pin.ensure(L.pin_total)) return false;
+    uint8_t* dw = c->dev[kDevWs].as<uint8_t>();
+    uint8_t* hp = c->pin.as<uint8_t>();
     PHD_HIP(hipMemsetAsync(dw, 0, L.a_bytes + L.c_bytes, st));
     const Context::Cls* cls = get_cls(c, gp);
     if (!cls) return false;

@@ -174,6 +174,8 @@ for _name, _res, _args in (*_report_prototypes(),
                            ("phd_debug_fft_split_pass", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
                            ("phd_install_crash_maps", ctypes.c_int, [ctypes.c_char_p]),
                            ("phd_debug_library_threads", ctypes.c_int, [ctypes.c_int]),
+                           ("phd_debug_context_bytes", ctypes.c_int,
+                            [P(ctypes.c_ulonglong), P(ctypes.c_ulonglong)]),
                            ("phd_debug_legacy_report", P(Full_Report_Data),
                             [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
                            # batch calls with per-image crop boxes (crops: n pointers to Crop_Boundaries)
