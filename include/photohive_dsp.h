@@ -951,6 +951,68 @@ int phd_stats_maps_device(const uint8_t* const* d_images, const int* heights, co
 int phd_debug_window_stats_host(const uint8_t* rgb, int height, int width, const Crop_Boundaries* windows,
                                 int window, double* stats, unsigned long long* sums);
 
+/* ---- palette maps: palette slot counts of window grids, on the device
+ * The window palette of a T x T window of a label map (what the _labels entries
+ * write: mh x mw uint16, row-major, PHD_LABEL_NONE for a pixel of no slot -- the
+ * lists of src/color_quantization.c:342-479 and :510-576 kept per pixel; the
+ * window in MAP coordinates, rows top <= y < top+T and columns left <= x <
+ * left+T, as phd_box_palettes_device takes the boxes of
+ * src/image_processing.c:213-232) of a palette of n_slots slots (0..4096) is the
+ * box palette's definition restricted to square windows, left on the device:
+ *  - counts: n_slots + 1 uint32.  Column s < n_slots is the number of the window's
+ *    T^2 elements whose label is s; column n_slots counts every other element
+ *    (PHD_LABEL_NONE and any label >= n_slots).  A row sums to T^2.  The integers
+ *    of phd_box_palettes_device and phd_debug_box_counts_host on the same boxes.
+ *  - dominant: one uint16, the column of the largest count over columns
+ *    0..n_slots, the lowest column on a tie, written as s for s < n_slots and as
+ *    PHD_LABEL_NONE for column n_slots ("none" wins only when strictly larger than
+ *    every slot; n_slots == 0 always gives PHD_LABEL_NONE).  A grid's dominant
+ *    values are a gh x gw label map of the same palette, which
+ *    phd_labels_to_rgb_device paints.
+ * No floating point: a window's values depend on its T^2 labels and n_slots only,
+ * the same on every run and wherever the window sits in a call.
+ *
+ * window is 16, 32, 64 or 128.  d_counts[i]: device pointer, 4-byte aligned,
+ * receives n_i x (n_slots[i] + 1) uint32, window-major; d_dominant[i]: device
+ * pointer, 2-byte aligned, receives n_i uint16 (n_i is windows[i]->N or gh * gw).
+ * Either array may be NULL and either may hold NULL entries -- not wanted for that
+ * map --, but a map that has windows needs one of the two.  Every counter of a
+ * wanted row is written (the caller zeroes nothing) and nothing else is.  Maps are
+ * device label maps of any sizes from T x T at any 2-byte aligned base; no byte
+ * outside a window's own labels is read (a 4-label unit's 8 bytes are read at
+ * their own address).
+ * Refused with -1 before any device work (also on a machine without a GPU),
+ * phd_last_error naming map and window: NULL arguments or both output arrays
+ * NULL, n_maps <= 0, a NULL map, a size below T, a window size outside the four,
+ * a box whose sides are not T or that leaves the map, a non-positive stride,
+ * n_slots[i] outside 0..4096, a map with windows and neither output, more than
+ * 2^31 - 1 windows; also a misaligned map or output.
+ * One launch (profile slot 18) takes every window of every map: 256-thread
+ * blocks, one window per block at 128 and 64 and one per wave at 32 and 16; the
+ * counters in LDS (sized by the call's largest palette, in several private copies
+ * for small palettes), folded and written by the block that counted the window;
+ * no global atomic, no zeroed buffer, no second launch.  Per call one table upload
+ * (a 24-byte record and a 16-byte destination per window) and no allocation.
+ * Enqueued on `stream` and not waited for, or (NULL) on the library's stream and
+ * waited for, as phd_pack_views_device.  A call with no window at all does no
+ * device work and returns 0.  0 or -1. */
+/* Window lists, as phd_stats_windows_device takes them, in map coordinates. */
+int phd_palette_windows_device(const uint16_t* const* d_labels, const int* map_heights, const int* map_widths,
+                               int n_maps, const int* n_slots, const Crop_Boundaries* const* windows, int window,
+                               uint32_t* const* d_counts, uint16_t* const* d_dominant, void* stream);
+/* A regular grid per map: window_grid's rule on the map's size, gh = (mh - T) / stride + 1,
+ * gw = (mw - T) / stride + 1, row-major; stride > 0, may be smaller (overlap) or larger than the window. */
+int phd_palette_maps_device(const uint16_t* const* d_labels, const int* map_heights, const int* map_widths,
+                            int n_maps, const int* n_slots, int window, int stride,
+                            uint32_t* const* d_counts, uint16_t* const* d_dominant, void* stream);
+/* Validation hook, host only (no GPU): the window palette kernel's twin -- the same
+ * unit walk, clamp and dominant key (pal_window.h) over one label map of host
+ * memory at any 2-byte aligned base.  counts: windows->N x (n_slots + 1) uint32;
+ * dominant: windows->N uint16; either may be NULL, not both when there are
+ * windows.  0, or -1 with phd_last_error. */
+int phd_debug_window_palette_host(const uint16_t* map, int mh, int mw, int n_slots, const Crop_Boundaries* windows,
+                                  int window, uint32_t* counts, uint16_t* dominant);
+
 /* Palette intermediates of one device-resident image, for bit-exact checks:
  * hist[TL] (arm_octree quantities), parents[*n_parents] (valid_parents in
  * palette order), kept[*n_parents] (pixels surviving group_irregular_pixels).
@@ -1063,7 +1125,7 @@ int phd_last_timings(double* ms, int n);
  * 6 pack_views, 7 classify_views, 8 decode_views, 9 yuv_views,
  * 10 palette_labels, 11 box_palettes, 12 box_stats, 13 the fp64 route's
  * planar_box_stats, 14 window_blur, 15 window_vectors, 16 window_sharp,
- * 17 window_stats).
+ * 17 window_stats, 18 window_palette).
  * phd_profile_kernels resets the counters; phd_profile_read returns the
  * accumulated milliseconds and launch count of one kernel. */
 int phd_profile_kernels(unsigned mask);

@@ -247,11 +247,11 @@ def _image_arrays(images, ptr=lambda im: im.data_ptr()):
             (ctypes.c_int * n)(*[int(im.shape[1]) for im in images]))
 
 
-def _window_entries(windows, n):
+def _window_entries(windows, n, noun="images"):
     """The per-image window lists of a call over n images (None: none for any)."""
     entries = list(windows) if windows is not None else [None] * n
     if len(entries) != n:
-        raise ValueError(f"windows has {len(entries)} entries for {n} images")
+        raise ValueError(f"windows has {len(entries)} entries for {n} {noun}")
     return entries
 
 
@@ -1037,16 +1037,19 @@ def _window_grids(images, window, stride, kw=None):
 def _window_call(name, images, counts, shapes, outputs, stream, call):
     """The device tensors of a window call and the call itself.  outputs: (per
     output array of the C entry its (dtype, trailing shape), or None for one not
-    asked for -- a NULL array; form); call(pointers, heights, widths, n, *output
-    arrays, stream handle) is the entry; form(*an image's tensors, each shaped
-    shapes[i] + its trailing shape) is the image's result."""
+    asked for -- a NULL array; form); a trailing shape given as a function is
+    called with the image's index (the palette maps' n_slots + 1 counters); call(pointers,
+    heights, widths, n, *output arrays, stream handle) is the entry; form(*an
+    image's tensors, each shaped shapes[i] + its trailing shape) is the image's
+    result."""
     import torch
     n = len(images)
     if n == 0:
         return []
     specs, form = outputs
-    outs = [None if s is None else [torch.empty((c,) + s[1], dtype=s[0], device=im.device)
-                                    for im, c in zip(images, counts)] for s in specs]
+    trail = lambda s, i: tuple(s[1](i) if callable(s[1]) else s[1])         # noqa: E731
+    outs = [None if s is None else [torch.empty((c,) + trail(s, i), dtype=s[0], device=im.device)
+                                    for i, (im, c) in enumerate(zip(images, counts))] for s in specs]
     live = [ts for ts in outs if ts is not None]
     if stream is not None:
         for t in sum(live, []):
@@ -1162,6 +1165,72 @@ def stats_maps_device(images, window=64, stride=None, stream=None):
     return _window_call("stats_maps_device", images, [g[0] * g[1] for g in grids], grids, _stats_outputs(), stream,
                         lambda ptrs, hs, ws, n, ps, s: lib.phd_stats_maps_device(
                             ptrs, hs, ws, n, int(window), stride, ps, s))
+
+
+def _label_maps(labels, reports_or_n_slots):
+    """The label preamble of a palette window call: (the int16 [mh, mw] device
+    tensors as a list, the C array of their palette slot counts and its values)."""
+    import torch
+    labels, slots = list(labels), list(reports_or_n_slots)
+    if len(labels) != len(slots):
+        raise ValueError(f"{len(labels)} label maps for {len(slots)} reports")
+    for m in labels:
+        if not isinstance(m, torch.Tensor) or m.dtype != torch.int16 or m.dim() != 2 or not m.is_contiguous() \
+                or m.numel() == 0 or not m.is_cuda:
+            raise ValueError("expected contiguous, non-empty int16 [mh, mw] device tensors")
+    ns = [(int(s) if isinstance(s, (int, np.integer)) else len(s.color_palette.colors)) for s in slots]
+    return labels, (ctypes.c_int * len(ns))(*ns), ns
+
+
+def _palette_outputs(ns, counts, dominant):
+    """_window_call's outputs of the palette window entries: per map the counts
+    shaped shapes[i] + (n_slots + 1,), the dominant labels shaped shapes[i], or the
+    pair (counts, dominant)."""
+    import torch
+    if not counts and not dominant:
+        raise ValueError("counts or dominant (or both) must be asked for")
+    # a slot count outside 0..4096 is the library's to refuse; its tensor only has to exist
+    return ([(torch.int32, lambda i: (min(max(ns[i], 0), 4096) + 1,)) if counts else None,
+             (torch.int16, ()) if dominant else None],
+            (lambda c, d: (c, d)) if counts and dominant else (lambda t: t))
+
+
+def palette_windows_device(labels, reports_or_n_slots, windows, window=64, counts=True, dominant=False, stream=None):
+    """The palette slot counts of every window of label maps, left on the device
+    (phd_palette_windows_device): per map a torch.int32 device tensor
+    [n, n_slots + 1] -- row k, column s the number of elements of window k whose
+    label is slot s, the last column those in no slot (-1, and any label >=
+    n_slots): box_palettes_device's integers on the same boxes -- and / or, with
+    dominant=True, a torch.int16 tensor [n]: the slot with the largest count, the
+    lowest on a tie, -1 where "no slot" is strictly the largest.  With both the
+    result is the pair (counts, dominant).  labels and reports_or_n_slots as
+    box_palettes_device takes them; windows: per map None, a Crop_Boundaries or a
+    sequence of (top, bottom, left, right) boxes of MAP coordinates whose sides are
+    `window` (16, 32, 64 or 128).  One launch takes every window of every map;
+    nothing is copied to the host; with stream= the call is enqueued on that stream
+    and the tensors are valid in its order."""
+    labels, ns_arr, ns = _label_maps(labels, reports_or_n_slots)
+    arr, keep = _window_array(_window_entries(windows, len(labels), "maps"))
+    n_win = [0 if cb is None else int(cb.N) for cb in keep]
+    return _window_call("palette_windows_device", labels, n_win, [(c,) for c in n_win],
+                        _palette_outputs(ns, counts, dominant), stream,
+                        lambda ptrs, hs, ws, n, pc, pd, s: lib.phd_palette_windows_device(
+                            ptrs, hs, ws, n, ns_arr, arr, int(window), pc, pd, s))
+
+
+def palette_maps_device(labels, reports_or_n_slots, window=64, stride=None, counts=True, dominant=False, stream=None):
+    """palette_windows_device over window_grid of every map, the grid formed by the
+    library (phd_palette_maps_device): per map a torch.int32 device tensor
+    [gh, gw, n_slots + 1] and / or a torch.int16 tensor [gh, gw].  The dominant
+    tensor is itself a label map of the same palette: quantize_device paints it."""
+    labels, ns_arr, ns = _label_maps(labels, reports_or_n_slots)
+    stride = window if stride is None else int(stride)
+    grids = [window_grid(int(m.shape[0]), int(m.shape[1]), window, stride)[1] if stride > 0 and window > 0
+             else (0, 0) for m in labels]
+    return _window_call("palette_maps_device", labels, [g[0] * g[1] for g in grids], grids,
+                        _palette_outputs(ns, counts, dominant), stream,
+                        lambda ptrs, hs, ws, n, pc, pd, s: lib.phd_palette_maps_device(
+                            ptrs, hs, ws, n, ns_arr, int(window), stride, pc, pd, s))
 
 
 def set_bounding_boxes(bounding_boxes):

@@ -137,8 +137,9 @@ bool gfft_run(const GfftPlan& p, const double2* in, double2* out, long count, do
 enum KernelId {
     kK1 = 0, kFftRows = 1, kFftCols = 2, kCutoffs = 3, kPalSums = 4, kSharp = 5, kPack = 6, kClassify = 7,
     kDecode = 8, kYuv = 9, kLabels = 10, kBoxPalettes = 11, kBoxStats = 12, kPlanarBoxStats = 13, kWindowBlur = 14,
-    kWindowVectors = 15, kWindowSharp = 16, kWindowStats = 17, kNumKernels = 18
+    kWindowVectors = 15, kWindowSharp = 16, kWindowStats = 17, kWindowPalette = 18, kNumKernels = 19
 };
+static_assert(kWindowPalette == kProfWindowPalette, "the window palette launch's profiler slot");
 static_assert(kWindowStats == kProfWindowStats, "the window statistics launch's profiler slot");
 static_assert(kWindowSharp == kProfWindowSharp, "the window sharpness launch's profiler slot");
 static_assert(kWindowVectors == kProfWindowVectors, "the blur vectors launch's profiler slot");

@@ -351,6 +351,18 @@ constexpr int kProfWindowStats = 17;
 struct StatWinRec;
 hipError_t launch_window_stats(int T, const StatWinRec* d_recs, double* const* d_dst, int n, hipStream_t st);
 
+// ---- window palettes (window_palette.hip; unit, copies rule and table: pal_window.h) --
+// Per T x T window (T = 16, 32, 64 or 128) of a palette label map its n_slots + 1
+// slot counts to d_dst[w].counts (4-byte aligned, or NULL) and its dominant label
+// to d_dst[w].dominant (2-byte aligned, or NULL): n windows, one launch.
+// lds_words: the largest pw_lds_words of the call's records, so that the launch's
+// LDS follows the call's palettes and not the 4097-counter maximum.
+constexpr int kProfWindowPalette = 18;
+struct PalWinRec;
+struct PalWinDst;
+hipError_t launch_window_palette(int T, const PalWinRec* d_recs, const PalWinDst* d_dst, int n, int lds_words,
+                                 hipStream_t st);
+
 // Row pass: luma - avg of two rows as one complex sequence, FFT, split, write
 // the half spectra column-major into inter[wf][height].
 // Runtime-plan FFT passes over a batch of same-size images in one launch each

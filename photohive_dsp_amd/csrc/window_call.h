@@ -5,7 +5,9 @@
 // (core.py's window_grid).  Every window entry validates, counts and walks its
 // windows through WindowPlan -- phd_blur_windows_device, the blur vector entries
 // (phd_blurwin.cpp) and the window sharpness entries (phd_sharpwin.cpp) -- and
-// their host twins share window_twin_why.  The rules' words live here and
+// their host twins share window_twin_why.  The palette window entries
+// (phd_palwin.cpp) take label maps the same way and say "map" where the others
+// say "image": the plan's and the ladder's `noun`.  The rules' words live here and
 // nowhere else; tests/native/window_call_asan.cpp runs the header alone.
 #pragma once
 
@@ -24,7 +26,8 @@ inline std::string window_too_small(int height, int width, int T) {
 
 // The list rule: no list or an empty one is fine; else every box is T x T inside
 // the height x width image (win_box_check).
-inline bool window_list_why(const Crop_Boundaries* b, int T, int height, int width, std::string* why) {
+inline bool window_list_why(const Crop_Boundaries* b, int T, int height, int width, std::string* why,
+                            const char* noun = "image") {
     if (!b || b->N == 0) return true;
     if (b->N < 0 || !b->top || !b->bottom || !b->left || !b->right) return *why = "bad window list", false;
     for (int k = 0; k < b->N; k++) {
@@ -34,7 +37,7 @@ inline bool window_list_why(const Crop_Boundaries* b, int T, int height, int wid
                                 std::to_string(b->bottom[k]) + ", left " + std::to_string(b->left[k]) + ", right " +
                                 std::to_string(b->right[k]) + ")";
         if (rule == 1) return *why = box + " is not " + std::to_string(T) + " x " + std::to_string(T), false;
-        return *why = box + " leaves the " + std::to_string(height) + " x " + std::to_string(width) + " image", false;
+        return *why = box + " leaves the " + std::to_string(height) + " x " + std::to_string(width) + " " + noun, false;
     }
     return true;
 }
@@ -49,18 +52,20 @@ struct WindowPlan {
     const Crop_Boundaries* const* windows;   // per image, NULL entries allowed; the grid entries have none
     bool lists;                              // windows[i]'s boxes, else the grid at `stride`
     int T, stride;
+    const char* noun;                        // what the messages call an input: "image", or "map"
     std::vector<long long> count;            // windows of image i
     long long total = 0;                     // at most 2^31 - 1 after build
 
     WindowPlan(const uint8_t* const* d_images_, const int* heights_, const int* widths_, int n_images_,
-               const Crop_Boundaries* const* windows_, bool lists_, int window, int stride_)
+               const Crop_Boundaries* const* windows_, bool lists_, int window, int stride_,
+               const char* noun_ = "image")
         : d_images(d_images_), heights(heights_), widths(widths_), n_images(n_images_), windows(windows_),
-          lists(lists_), T(window), stride(stride_) {}
+          lists(lists_), T(window), stride(stride_), noun(noun_) {}
 
     // rest: whether the entry's other required pointers are there
     bool args_why(bool rest, std::string* why) const {
         if (!d_images || !heights || !widths || (lists && !windows) || !rest) return *why = "NULL argument", false;
-        if (n_images <= 0) return *why = "n_images must be positive", false;
+        if (n_images <= 0) return *why = std::string("n_") + noun + "s must be positive", false;
         return true;
     }
 
@@ -73,13 +78,13 @@ struct WindowPlan {
         gws_.assign(n_images, 0);
         total = 0;
         for (int i = 0; i < n_images; i++) {
-            const std::string img = "image " + std::to_string(i) + ": ";
-            if (!d_images[i]) return *why = img + "NULL image", false;
+            const std::string img = std::string(noun) + " " + std::to_string(i) + ": ";
+            if (!d_images[i]) return *why = img + "NULL " + noun, false;
             if (heights[i] < T || widths[i] < T)
                 return *why = img + window_too_small(heights[i], widths[i], T), false;
             if (lists) {
                 std::string list_why;
-                if (!window_list_why(windows[i], T, heights[i], widths[i], &list_why))
+                if (!window_list_why(windows[i], T, heights[i], widths[i], &list_why, noun))
                     return *why = img + list_why, false;
                 count[i] = windows[i] ? windows[i]->N : 0;
             } else {
@@ -117,11 +122,12 @@ private:
 // window size (size_why: its refusal, or empty), the size, the list, and the
 // outputs wherever there is a window (no_outputs: the twin's words for theirs).
 inline bool window_twin_why(const uint8_t* rgb, int height, int width, const Crop_Boundaries* windows, int T,
-                            const std::string& size_why, bool outputs, const char* no_outputs, std::string* why) {
-    if (!rgb) return *why = "NULL image", false;
+                            const std::string& size_why, bool outputs, const char* no_outputs, std::string* why,
+                            const char* noun = "image") {
+    if (!rgb) return *why = std::string("NULL ") + noun, false;
     if (!size_why.empty()) return *why = size_why, false;
     if (height < T || width < T) return *why = window_too_small(height, width, T), false;
-    if (!window_list_why(windows, T, height, width, why)) return false;
+    if (!window_list_why(windows, T, height, width, why, noun)) return false;
     if (windows && windows->N > 0 && !outputs) return *why = no_outputs, false;
     return true;
 }

@@ -123,6 +123,7 @@ WINDOW_BLUR_KERNEL = 14    # the window blur's one-block-per-window kernel (bit 
 WINDOW_VECTORS_KERNEL = 15  # the blur vectors' kernel: the same block finishes the window (bit 15: "window_vectors")
 WINDOW_SHARP_KERNEL = 16   # the sharpness maps' kernel (bit 16: "window_sharp")
 WINDOW_STATS_KERNEL = 17   # the statistics maps' kernel (bit 17: "window_stats")
+WINDOW_PALETTE_KERNEL = 18  # the palette maps' kernel (bit 18: "window_palette")
 LABEL_NONE = 0xFFFF      # PHD_LABEL_NONE: a pixel in no palette slot's list (-1 as int16)
 lib.phd_debug_time_kernel.restype = ctypes.c_int
 lib.phd_debug_time_kernel.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, P(PhdConfig),
@@ -266,6 +267,16 @@ for _name, _res, _args in (*_report_prototypes(),
                            ("phd_debug_window_stats_host", ctypes.c_int,
                             [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, P(Crop_Boundaries), ctypes.c_int,
                              ctypes.c_void_p, ctypes.c_void_p]),
+                           # palette maps: per 16- to 128-px window of a label map, slot counts and the dominant slot
+                           ("phd_palette_windows_device", ctypes.c_int,
+                            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                             P(P(Crop_Boundaries)), ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+                           ("phd_palette_maps_device", ctypes.c_int,
+                            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                             ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+                           ("phd_debug_window_palette_host", ctypes.c_int,
+                            [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, P(Crop_Boundaries),
+                             ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
                            # which palette kernels a configuration takes (host only)
                            ("phd_debug_palette_path", ctypes.c_int, [P(PhdConfig), ctypes.c_int])):
     try:
